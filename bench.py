@@ -2,8 +2,14 @@
 """bench.py -- train-step samples/s of ResNet-20 / CIFAR-10, 8-bit DFXP, on 1..8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch B [--bn sync|local]]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line. ``--full`` adds what takes
+runs of its own: the live roofline of the dominant kernel and the CPU baseline (the oracle's step on the
+host). ``--dump-outputs DIR`` writes what the last timed step left (loss, logits, parameters, momentum,
+DFXP exponents) as ``DIR/<name>.npy``; with the same arguments the inputs are the same from run to run.
 
 A step is one ``Trainer.step`` (reference trainer.py:157): forward, mean softmax-CE, manual
 backward through all 192 DFXP quantisers, MomentumOptimizer update and the update_range
@@ -201,6 +207,31 @@ def _exchange_report(trainer, model, world, reps=20):
     return rep
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: the files' array data in all
+DUMP_SAMPLE_SEED = 20
+
+
+def dump_outputs(path, trainer, model):
+    """--dump-outputs: what the last timed step left with its caller, one ``<name>.npy`` each: the loss and
+    logits of that step's batch, the updated parameters and momentum accumulators (the flat buffers, in
+    grads_and_vars order) and every quantiser's exponent. float32 as computed; the integer exponents as
+    float64. An array over its share of the budget (ResNet-50's parameters) is written as a fixed sample:
+    the elements at sorted indices drawn without replacement by numpy's PCG64 from DUMP_SAMPLE_SEED."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": model.loss, "weights": trainer.flat.w, "momentum": trainer.flat.a,
+              "exponents": trainer.ctx.exps[:len(trainer.ctx.quantizers)]}
+    if getattr(model, "logits", None) is not None:
+        arrays["logits"] = model.logits
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _dry_run(args, world, rank, backend, strong):
     if backend != "gloo":
         raise SystemExit("--dry-run runs on the gloo backend (CPU)")
@@ -245,9 +276,15 @@ def main():
                          "samples/s at 32 / 64 / 128 / 256)")
     ap.add_argument("--eager", action="store_true", help="no HIP graph (diagnostics)")
     ap.add_argument("--layerwise", action="store_true", help="run the Layer_q path instead of the fused plan")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the live roofline of "
+                         "the dominant kernel and the CPU baseline (one GPU only); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (loss, logits, parameters, momentum, "
+                         "DFXP exponents) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (CPU, gloo): each step is one all-reduce of a "
                          "small CPU tensor; used by the CPU tests, never a measurement")
@@ -263,6 +300,8 @@ def main():
     w4 = args.workload == "resnet20w4"
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_launch_ranks(args.gpus))
 
@@ -338,6 +377,8 @@ def main():
     el = _timed_region(lambda i: trainer.step(xs[i % 4], ys[i % 4]), args.steps, args.warmup, world,
                        torch.cuda.synchronize, device)
     loss = float(model.loss.item())
+    if args.dump_outputs and rank == 0:  # before anything below runs another step
+        dump_outputs(args.dump_outputs, trainer, model)
 
     out = {
         "metric": METRIC_R50 if r50 else (METRIC_W4 if w4 else METRIC),
@@ -377,7 +418,7 @@ def main():
     # it can diverge (identically in the oracle) without changing the work per step: flagged here
     ncls = 1000 if r50 else 10
     out["config"]["loss_diverged"] = bool(not math.isfinite(loss) or loss > 10 * math.log(ncls))
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         from lbt_amd.roofline import measure_dominant
         tf = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles",
                           "pmc_traffic_resnet50.json" if r50 else "pmc_traffic.json")
@@ -394,7 +435,7 @@ def main():
                 sg = SURVEY_STEP_BYTES_R20 / (el / args.steps) / 1e9
                 out["roofline"]["step"]["frac_survey_model"] = round(sg / out["roofline"]["peak"], 4)
                 out["roofline"]["step"]["survey_model_bytes"] = int(SURVEY_STEP_BYTES_R20)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_r50(args.cpu_seconds) if r50 else cpu_baseline(args.cpu_seconds, args.batch)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -9,8 +9,8 @@
 #   tests            the whole -m gpu suite
 #   tests:<path>[:<k>]  a subset: tests:tests/test_gpu_parity.py  or  tests:tests:fused or golden
 #   smoke            __graft_entry__.smoke()
-#   bench[:args]     bench.py (default arguments, or the ':'-separated extra ones, e.g. bench:--batch:16)
-#   r50              bench.py --workload resnet50 --steps 20 --warmup 5
+#   bench[:args]     bench.py --full (default arguments, or the ':'-separated extra ones, e.g. bench:--batch:16)
+#   r50              bench.py --full --workload resnet50 --steps 20 --warmup 5 --no-cpu-baseline
 #   trace:<B>        rocprofv3 kernel trace of the graph-replayed fused step at per-GPU batch B, summarised
 #                    per launch position (tools/step_positions.py)
 #   strong           tools/strong_probe.py (per-GPU batch 16/32/64/128 + world-1 RCCL exchange)
@@ -42,10 +42,10 @@ run_step() {
       timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$log.log" 2>&1; rc=$?
       tail -1 "$log.log" ;;
     bench)
-      timeout -k 10 400 python bench.py $args > "$log.json" 2> "$log.err"; rc=$?
+      timeout -k 10 400 python bench.py --full $args > "$log.json" 2> "$log.err"; rc=$?
       cut -c1-700 "$log.json" ;;
     r50)
-      timeout -k 10 400 python bench.py --workload resnet50 --steps 20 --warmup 5 --no-cpu-baseline $args \
+      timeout -k 10 400 python bench.py --full --workload resnet50 --steps 20 --warmup 5 --no-cpu-baseline $args \
         > "$log.json" 2> "$log.err"; rc=$?
       cut -c1-400 "$log.json" ;;
     trace)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect one round's measurement artifacts on the GPU box (run from the repo root via gpurun):
 #   tools/profile_round.sh <tag> [bench args]   e.g.  tools/profile_round.sh r01 ; ... r01_r50 --workload resnet50
-# -> gpurun_out/prof_<tag>/: bench.json (default bench: roofline + cpu_baseline), kernel-trace
+# -> prof_<tag>/ in the job's output folder: bench.json (bench.py --full: roofline + cpu_baseline), kernel-trace
 #    stats of the graph-replayed step, and FETCH_SIZE / WRITE_SIZE passes (separate, as the
 #    MI355X guide prescribes; eager mode) summarised into pmc_traffic.json.
 set -euo pipefail
@@ -11,7 +11,7 @@ EXTRA="$*"  # extra bench.py arguments, e.g. --workload resnet50
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
-timeout -k 10 400 python bench.py $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python bench.py --full $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
   python bench.py $EXTRA --steps 50 --warmup 10 --no-cpu-baseline --no-roofline > "$OUT/stats.log" 2>&1
