@@ -1238,11 +1238,9 @@ constexpr int kBThreads = kBNW * 64;
 // image rows per workgroup: 8 for the 16-channel stage (1024 4-row tiles would take two rounds of
 // two 512-thread workgroups per CU), 4 otherwise (W * C == 512: a 4-row tile is 8 MFMA tiles)
 __host__ __device__ constexpr int tile_rows(int CS) { return CS == 1 ? 8 : 4; }
-// phase-1 (halo) channel-quad groups per thread
-__host__ __device__ constexpr int halo_iters(int CS, int TH) {
-  return ((TH + 2) * (512 / (CS * 16) + 2) * CS * 4 + kBThreads - 1) / kBThreads;
-}
-__host__ __device__ constexpr int halo_iters(int CS) { return halo_iters(CS, tile_rows(CS)); }
+// phase-1 (halo) channel-quad groups per thread: the TH + 2 halo rows' in-image pixels only (W * C / 4
+// == 128 groups per row); the padding cells of the LDS halo image are filled by halo_pad_fill
+__host__ __device__ constexpr int halo_iters(int TH) { return ((TH + 2) * 128 + kBThreads - 1) / kBThreads; }
 // Batch-adaptive tile rows of the fused conv kernels: the 16-channel stage takes 4-row tiles when its
 // 8-row tiles leave the launch with fewer workgroups than CUs (N * H / 8 < 256: per-GPU batches below
 // 64 -- the strong-scaling shards of configs[2]): twice the workgroups, each with two thirds of the halo
@@ -1311,6 +1309,28 @@ struct WImg {
       return *reinterpret_cast<const v4i*>(lds + col * kStride + slice * 16);
   }
 };
+
+// Phase 1 of the fused conv kernels enumerates only the halo rows inside the image (rows ylo .. yhi =
+// max(row0 - 1, 0) .. min(row0 + TH, H - 1), wave-uniform) and the columns 0 .. W - 1: no loads and no
+// element chain on the conv's zero padding. The padding cells of the LDS halo image [(TH+2)][(W+2)][C]
+// -- the left and right columns of every halo row, and the whole top / bottom row of a tile at the image
+// edge -- take the padding code `word` (four codes) by plain stores, from the highest threads first:
+// the waves the last phase-1 iteration leaves without a group. Before the barrier that ends phase 1.
+template <int C, int TH>
+LBT_DEV void halo_pad_fill(int8_t* img, int row0, int H, int word) {
+  constexpr int C4 = C / 4, W = 512 / C, Wp = W + 2;
+  constexpr int kSide = (TH + 2) * 2 * C4;  // (halo row, left | right, channel quad)
+  static_assert(kSide <= kBThreads && W * C4 <= kBThreads, "one padding word per thread and kind");
+  const int t = kBThreads - 1 - (int)threadIdx.x;
+  if (t < kSide) {
+    const int hy = t / (2 * C4), side = (t / C4) & 1, q = t % C4;
+    *reinterpret_cast<int*>(img + (hy * Wp + side * (W + 1)) * C + q * 4) = word;
+  }
+  if (t < W * C4) {  // a row's cells of columns 0 .. W - 1 are consecutive
+    if (row0 == 0) *reinterpret_cast<int*>(img + C + t * 4) = word;
+    if (row0 + TH >= H) *reinterpret_cast<int*>(img + ((TH + 1) * Wp + 1) * C + t * 4) = word;
+  }
+}
 
 struct ConvBwdArgs {
   lbt_chain_bwd_b b;
@@ -1481,7 +1501,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   // J: phase-3 groups per thread (NQ channel quads per tile: TH x 512 bytes / 4); NPR: (m, n) MFMA
   // pairs per tile (2 TH: one per wave at TH = 4). Two-row tiles (TH = 2, the under-filled 32- /
   // 64-channel launches) leave waves 4-7 without a pair and threads >= 256 without a phase-3 group.
-  constexpr int kBIt = halo_iters(CS, TH), NQ = TH * 128, J = (NQ + kBThreads - 1) / kBThreads, NPR = 2 * TH;
+  constexpr int kBIt = halo_iters(TH), NQ = TH * 128, J = (NQ + kBThreads - 1) / kBThreads, NPR = 2 * TH;
   static_assert(TH % 4 == 0 || TH == 2, "whole groups of 4 rows, or 2-row tiles");
   using WI = WImg<C, 4 * kMaxKS, W4>;
   union Smem {
@@ -1525,17 +1545,16 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   }
   LBT_TSS(1);  // the statistics loads issued
   // then every load that does not depend on the sums
-  // phase-1 operands: G / q codes and the output quantiser's noise over the halo rows
-  const int ngrp = (TH + 2) * Wp * C4;
+  // phase-1 operands: G / q codes and the output quantiser's noise over the halo rows inside the image
+  // (rows ylo .. yhi, whole rows of W pixels: group g is pixel g / C4 of them; halo_pad_fill)
+  const int ylo = row0 > 0 ? row0 - 1 : 0, yhi = row0 + TH < H ? row0 + TH : H - 1;
+  const int ngrp = (yhi - ylo + 1) * W * C4;  // a multiple of 128: whole waves
   int Gv[kBIt], Qv[kBIt];
   float4 Uv[kBIt];
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
     const int g = tid + it * kBThreads;
-    const int pix = g / C4, hy = pix / Wp, hx = pix - hy * Wp;
-    const int y = row0 - 1 + hy, x = hx - 1;
-    const bool in = g < ngrp && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    const uint32_t off = in ? (uint32_t)((y * W + x) * C + cq) : 0u;
+    const uint32_t off = g < ngrp ? (uint32_t)((ylo * W + g / C4) * C + cq) : 0u;
     Gv[it] = ld4i8(B.G, img + off);
     Qv[it] = ld4i8(B.qn_codes, img + off);
     Uv[it] = ld4f(B.qo.noise, off);
@@ -1610,13 +1629,12 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   int s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
-    if (it * kBThreads >= ngrp) break;  // uniform
+    if (it * kBThreads + wave * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
     const int g = tid + it * kBThreads;
-    const int pix = g / C4, hy = pix / Wp, hx = pix - hy * Wp;
-    const int y = row0 - 1 + hy, x = hx - 1;
-    const bool valid = g < ngrp;
-    const bool in = valid && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    const bool own = in && hy >= 1 && hy <= TH;
+    const int ry = g / (W * C4), x = g / C4 - ry * W;
+    const int y = ylo + ry, hy = y - row0 + 1;
+    const int pix = hy * Wp + x + 1;  // the pixel's cell of the LDS halo image
+    const bool own = hy >= 1 && hy <= TH;
     const float T1 = ov_thr(own, so.L), T2 = ov_thr(own, so.Lh);
     int G[4], q[4], c[4];
     unpack4(Gv[it], G);
@@ -1634,10 +1652,10 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       const f2 xm = dx * so.m;
       ov_count2(xm, T1, T2, ovq1, ovq2);
       const f2 fl = qfloor2(so, xm, u[h]);
-      c[2 * h] = in ? (int)fl.x : 0;  // outside the image: the conv's zero padding
-      c[2 * h + 1] = in ? (int)fl.y : 0;
+      c[2 * h] = (int)fl.x;
+      c[2 * h + 1] = (int)fl.y;
     }
-    if (valid) *reinterpret_cast<int*>(sh.gq + pix * C + cq) = pack4(c);
+    *reinterpret_cast<int*>(sh.gq + pix * C + cq) = pack4(c);
     if (own) {
       st_out(B.gq + img + (uint32_t)((y * W + x) * C + cq), pack4(c));
 #pragma unroll
@@ -1648,6 +1666,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
     }
   }
   pin_counts(ovq1, ovq2);
+  halo_pad_fill<C, TH>(sh.gq, row0, H, 0);  // outside the image: the conv's zero padding
   WI::store(sh.w, wimg);
   __syncthreads();
   LBT_TSB(2);
@@ -2428,7 +2447,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   constexpr int C = CS * 16, C4 = C / 4, NT = CS, W = 512 / C, Wp = W + 2;
   constexpr int kMaxKS = (9 * CS + 3) / 4;
   // (as conv_bwd_kernel: NQ channel quads and NPR MFMA pairs per tile; 2-row tiles idle half of each)
-  constexpr int kBIt = halo_iters(CS, TH), NQ = TH * 128, J = (NQ + kBThreads - 1) / kBThreads, NPR = 2 * TH;
+  constexpr int kBIt = halo_iters(TH), NQ = TH * 128, J = (NQ + kBThreads - 1) / kBThreads, NPR = 2 * TH;
   static_assert(TH % 4 == 0 || TH == 2, "whole groups of 4 rows, or 2-row tiles");
   using WI = WImg<C, 4 * kMaxKS, W4>;
   __shared__ __attribute__((aligned(16))) FwdShared<C, TH, WI::kBytes> sh;
@@ -2461,16 +2480,15 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       sv[i][1] = cs[(int64_t)i * 2 * C + C];
     }
   }
-  const int ngrp = (TH + 2) * Wp * C4;
+  // (as conv_bwd_kernel: the halo rows ylo .. yhi inside the image, whole rows of W pixels; halo_pad_fill)
+  const int ylo = row0 > 0 ? row0 - 1 : 0, yhi = row0 + TH < H ? row0 + TH : H - 1;
+  const int ngrp = (yhi - ylo + 1) * W * C4;  // a multiple of 128: whole waves
   int qv[NB][kBIt];
   float4 rv[kBIt], nrv[NB][kBIt], nov[kBIt];
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
     const int g = tid + it * kBThreads;
-    const int pix = g / C4, hy = pix / Wp, hx = pix - hy * Wp;
-    const int y = row0 - 1 + hy, x = hx - 1;
-    const bool in = g < ngrp && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    const uint32_t off = in ? (uint32_t)((y * W + x) * C + cq) : 0u;
+    const uint32_t off = g < ngrp ? (uint32_t)((ylo * W + g / C4) * C + cq) : 0u;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       const lbt_chain_branch& Bb = b == 0 ? a.b1 : a.b2;
@@ -2563,13 +2581,12 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   int ovr[2][2] = {{0, 0}, {0, 0}}, ovx1 = 0, ovx2 = 0;
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
-    if (it * kBThreads >= ngrp) break;  // uniform
+    if (it * kBThreads + wave * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
     const int g = tid + it * kBThreads;
-    const int pix = g / C4, hy = pix / Wp, hx = pix - hy * Wp;
-    const int y = row0 - 1 + hy, x = hx - 1;
-    const bool valid = g < ngrp;
-    const bool in = valid && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    const bool own = in && hy >= 1 && hy <= TH;
+    const int ry = g / (W * C4), x = g / C4 - ry * W;
+    const int y = ylo + ry, hy = y - row0 + 1;
+    const int pix = hy * Wp + x + 1;  // the pixel's cell of the LDS halo image
+    const bool own = hy >= 1 && hy <= TH;
     const uint32_t e = (uint32_t)((y * W + x) * C + cq);
     f2 v[2];  // the channel quad as two packed pairs
     float T1[2], T2[2];
@@ -2619,14 +2636,15 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       co[2 * h] = floor_i(fminf(w.x, so1.Lm1));
       co[2 * h + 1] = floor_i(fminf(w.y, so1.Lm1));
     }
-    // LBT_OUT_U8OFF: code - 128 (= code ^ 0x80 for codes in [0, 255]); outside the image: the code of 0
-    const int cw = in ? (pack4(co) ^ (int)0x80808080) : (int)0x80808080;
-    if (valid) *reinterpret_cast<int*>(sh.x + pix * C + cq) = cw;
+    // LBT_OUT_U8OFF: code - 128 (= code ^ 0x80 for codes in [0, 255])
+    const int cw = pack4(co) ^ (int)0x80808080;
+    *reinterpret_cast<int*>(sh.x + pix * C + cq) = cw;
     if (own) st_out((int8_t*)a.o1 + img + e, cw);
   }
 #pragma unroll
   for (int b = 0; b < NB; ++b) pin_counts(ovr[b][0], ovr[b][1]);
   pin_counts(ovx1, ovx2);
+  halo_pad_fill<C, TH>(sh.x, row0, H, (int)0x80808080);  // outside the image: the offset code of 0
   WI::store(sh.w, wimg);
   __syncthreads();
   LBT_TS(2);
