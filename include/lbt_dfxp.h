@@ -574,6 +574,12 @@ typedef struct lbt_conv_fwd {
 } lbt_conv_fwd;
 int lbt_conv_fwd_fused_i8(const lbt_conv_fwd* p, void* stream);
 
+/* Image rows per workgroup that lbt_conv_bwd_fused_i8 / lbt_conv_fwd_fused_i8 launch with for a conv of
+ * Cin (= Cout) channels on N samples of H rows: 8, 4 or 2 (batch-adaptive; the LBT_TILE_ROWS1 /
+ * LBT_TILE_ROWS23 environment overrides included), so both launch N * (H / rows) tile workgroups.
+ * Host only: nothing is launched. -LBT_EINVAL for a Cin that is not 16, 32 or 64.               */
+int lbt_conv_fused_tile_rows(int32_t Cin, int64_t N, int32_t H);
+
 /* BN backward passes A and B for 9..16-bit gradient quantisers (config 4): the arithmetic of
  * lbt_bn_chain_bwd_a / _b (one branch, no mask) with int16 grad codes and int64 channel sums.
  * Rows here are pixels: g / R / qn / gout / dout / dx are [rows][C]; inner = the per-sample

@@ -21,16 +21,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-LBT_DEV void load4_i8(const int8_t* p, int64_t i, int v[4]) {
-  const char4 c = *reinterpret_cast<const char4*>(p + i);
-  v[0] = c.x; v[1] = c.y; v[2] = c.z; v[3] = c.w;
-}
-LBT_DEV void unpack4_i8(int w, int v[4]) {
-  v[0] = (int8_t)(w & 0xff); v[1] = (int8_t)((w >> 8) & 0xff);
-  v[2] = (int8_t)((w >> 16) & 0xff); v[3] = (int8_t)(w >> 24);
-}
-LBT_DEV int ld_i8x4(const int8_t* p, int64_t i) { return *reinterpret_cast<const int*>(p + i); }
-LBT_DEV float4 ld_f32x4(const float* p, int64_t i) { return *reinterpret_cast<const float4*>(p + i); }
 LBT_DEV void f4(const float4& c, float v[4]) { v[0] = c.x; v[1] = c.y; v[2] = c.z; v[3] = c.w; }
 
 // Rows are processed in batches of kRB: every load of a batch is issued before any of its

@@ -1,5 +1,5 @@
 // chain_flags.h -- configuration words of the element-chain kernels (bn.hip) and of the GEMM
-// epilogues that run the same chains (conv_mfma.hip): each launch's descriptor is reduced to a
+// epilogues that run the same chains (conv_mfma.hip, conv_fused.h): each launch's descriptor is reduced to a
 // flag word on the host, and the combinations the fused ResNet plan uses are compiled as their
 // own kernel variants (no per-element branches); kRt selects the run-time-descriptor variant.
 #pragma once
@@ -29,6 +29,7 @@ enum : int {
   kAStoch = 8,   // every quantiser stochastic
   kAFB = 16,     // every branch: both quantisers active, int8 G codes and sums out
 };
+constexpr int kAFused = kAFB | kAStoch;  // what every GEMM-fused pass A requires
 
 enum : int {
   kBQ = 1,      // quantised gq output (else fp32 dx)

@@ -16,6 +16,11 @@
 
 namespace lbt {
 
+inline bool desc_ok(const lbt_conv_desc& d) {
+  return d.N > 0 && d.H > 0 && d.W > 0 && d.KH > 0 && d.KW > 0 && d.SH > 0 && d.SW > 0 && d.Ho > 0 &&
+         d.Wo > 0 && d.Cin > 0 && d.Cout > 0;
+}
+
 struct QOut {
   int8_t* yq;       // [M][ncol] int8 codes
   lbt_qdesc q;

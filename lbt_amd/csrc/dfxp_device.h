@@ -449,6 +449,41 @@ LBT_DEV int chan_scatter4(const int v[4], int period) {
 LBT_DEV bool chan_scatter_ok(int period) { return period >= 1 && period <= 16; }
 LBT_DEV bool chan_scatter_owner(int period) { return (int)(threadIdx.x & 15) < period; }
 
+// A lane's own row / half plus the paired one: v_permlane16_swap's two results hold the lane's own
+// 16-lane row and the paired row, both ways (a VALU exchange where __shfl_xor(v, 16) was an LDS
+// ds_bpermute round trip); v_permlane32_swap's the lane's own half and the other half.
+LBT_DEV int row_pair_sum(int v) {
+  const auto h = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  return (int)h[0] + (int)h[1];
+}
+LBT_DEV int half_pair_sum(int v) {
+  const auto h = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return (int)h[0] + (int)h[1];
+}
+// 64-bit sum over the four 16-lane rows of a wave (permlane16 then permlane32 swaps on both halves)
+LBT_DEV long long rows_total64(long long v) {
+  const uint32_t lo = (uint32_t)v, hi = (uint32_t)((unsigned long long)v >> 32);
+  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  v = (long long)(((unsigned long long)b[0] << 32) | a[0]) + (long long)(((unsigned long long)b[1] << 32) | a[1]);
+  const uint32_t lo2 = (uint32_t)v, hi2 = (uint32_t)((unsigned long long)v >> 32);
+  const auto c = __builtin_amdgcn_permlane32_swap(lo2, lo2, false, false);
+  const auto d = __builtin_amdgcn_permlane32_swap(hi2, hi2, false, false);
+  return (long long)(((unsigned long long)d[0] << 32) | c[0]) + (long long)(((unsigned long long)d[1] << 32) | c[1]);
+}
+
+// Four consecutive int8 codes as one 32-bit word (load, unpack, pack) and four consecutive floats
+LBT_DEV int ld_i8x4(const int8_t* p, int64_t i) { return *reinterpret_cast<const int*>(p + i); }
+LBT_DEV float4 ld_f32x4(const float* p, int64_t i) { return *reinterpret_cast<const float4*>(p + i); }
+LBT_DEV void unpack4_i8(int w, int v[4]) {
+  v[0] = (int8_t)(w & 0xff); v[1] = (int8_t)((w >> 8) & 0xff);
+  v[2] = (int8_t)((w >> 16) & 0xff); v[3] = (int8_t)(w >> 24);
+}
+LBT_DEV int pack4_i8(const int c[4]) {
+  return (int)((uint32_t)(c[0] & 0xff) | ((uint32_t)(c[1] & 0xff) << 8) | ((uint32_t)(c[2] & 0xff) << 16) |
+               ((uint32_t)c[3] << 24));
+}
+
 // MomentumOptimizer.apply_gradients (trainer.py:81-82) on element i: a = mu*a + g*gscale; w -= lr*a.
 // update_range on one slot from its total counters (dynamic_fixed_point.py:70-94).
 LBT_DEV void range_apply(int i, int c1, int c2, int32_t* exps, const int32_t* bits, const float* target,

@@ -193,18 +193,6 @@ LBT_DEV void head_pass_a(const lbt_chain_bwd_a& a, int n, int HW, int C, int q0,
   }
 }
 
-// 64-bit sum over the four 16-lane rows of a wave (v_permlane16 / 32 swaps on both halves)
-LBT_DEV long long head_rows_total64(long long v) {
-  const uint32_t lo = (uint32_t)v, hi = (uint32_t)((unsigned long long)v >> 32);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  v = (long long)(((unsigned long long)b[0] << 32) | a[0]) + (long long)(((unsigned long long)b[1] << 32) | a[1]);
-  const uint32_t lo2 = (uint32_t)v, hi2 = (uint32_t)((unsigned long long)v >> 32);
-  const auto c = __builtin_amdgcn_permlane32_swap(lo2, lo2, false, false);
-  const auto d = __builtin_amdgcn_permlane32_swap(hi2, hi2, false, false);
-  return (long long)(((unsigned long long)d[0] << 32) | c[0]) + (long long)(((unsigned long long)d[1] << 32) | c[1]);
-}
-
 // The end chain's Normalization_q moment sums (the chain's sharded [32][2C] channel sums), issued as
 // the launch's FIRST loads: wave w owns channels 16 w .. 16 w + 15 (C <= 64), lane l channel
 // 16 w + (l & 15) of shards 8 (l >> 4) .. + 7 -- each load instruction covers 4 shards x 16 channels.
@@ -231,8 +219,8 @@ LBT_DEV void head_stat_finish(const lbt_bn_norm& b, int C, const HeadStat& hs, f
     S1 += hs.v[i][0];
     S2 += hs.v[i][1];
   }
-  S1 = head_rows_total64(S1);
-  S2 = head_rows_total64(S2);
+  S1 = rows_total64(S1);
+  S2 = rows_total64(S2);
   const int c = wave * 16 + (lane & 15);
   if (lane < 16 && c < C) {
     const double s = ldexp(1.0, -frac_exp(b.qn));

@@ -2412,7 +2412,7 @@ namespace {
 // dW[tap][ci][co] = sum_p x[p shifted by tap][ci] * g[p][co] for the wide layers. x is offset int8
 // (x' = x - 128, post-ReLU 9-bit codes 0..255); g is int8 or int16 (G16: g = 256 gh + gl' + 128).
 // Per workgroup: one tap, 64 ci x 64 co, a pixel range; each wave walks 64-pixel chunks, stores
-// [pixel][16 B] LDS images and multiplies ds_read_b64_tr_b8 fragments (as conv_mfma.hip's wgrad).
+// [pixel][16 B] LDS images and multiplies ds_read_b64_tr_b8 fragments (as conv_wgrad_body.h's wgrad).
 // Exact identity (over every processed lane, invalid ones carrying x' = -128, g = 0):
 //   sum x g = 256 sum x' gh + sum x' gl' + 128 sum x' + 128 (256 sum gh + sum gl' + 128 npix)
 // (G8: sum x g = sum x' g + 128 sum g); the row / column sums come from MFMAs against ones.

@@ -24,4 +24,21 @@ LBT_DEV v4i tr_frag(const int8_t* img, int base, int lane) {
   return v4i{lo.x, lo.y, hi.x, hi.y};
 }
 
+// 16 signed 4-bit codes (element e = nibble e: low nibble of byte e/2 first) -> 16 int8 lanes of an
+// MFMA operand: lo / hi nibbles interleaved with v_perm_b32, then sign-extended bytewise without
+// carries: (b & 7) | ((b & 8) * 0x1F) sets bits 3-7 exactly when bit 3 (the sign) is set.
+LBT_DEV v4i unpack_i4x16(v2i pk) {
+  v4i o;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const uint32_t x = (uint32_t)(w == 0 ? pk.x : pk.y);
+    const uint32_t lo = x & 0x0F0F0F0Fu, hi = (x >> 4) & 0x0F0F0F0Fu;
+    const uint32_t a = __builtin_amdgcn_perm(hi, lo, 0x05010400u);  // e0 e1 e2 e3
+    const uint32_t b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);  // e4 e5 e6 e7
+    o[2 * w] = (int)((a & 0x07070707u) | ((a & 0x08080808u) * 0x1Fu));
+    o[2 * w + 1] = (int)((b & 0x07070707u) | ((b & 0x08080808u) * 0x1Fu));
+  }
+  return o;
+}
+
 }  // namespace lbt

@@ -1,13 +1,14 @@
-// pk2.h -- channel pairs on packed fp32 for the element-chain kernels (bn.hip, bn_wide.hip).
+// pk2.h -- channel pairs on packed fp32 for the element-chain kernels (bn.hip, bn_wide.hip, head.hip, the
+// fused conv kernels of conv_fused.h).
 #pragma once
 #include "dfxp_device.h"
 
 namespace lbt {
 
 // The quantisers' last steps for an ACTIVE quantiser (L >= 1) and a non-NaN operand -- every caller of the
-// packed helpers below: the clip is one v_med3_f32 (fminf(fmaxf(v, -L), L - 1) needs two; the fused conv
-// kernels' qfloor2 already clips this way), and floor + conversion is one v_cvt_flr_i32_f32 (exact: |v|
-// <= 2^15). The element chains are VALU-bound (profiles/round5/chain_pmc.txt).
+// packed helpers below: the clip is one v_med3_f32 (fminf(fmaxf(v, -L), L - 1) needs two), and floor +
+// conversion is one v_cvt_flr_i32_f32 (exact: |v| <= 2^15). The element chains are VALU-bound
+// (profiles/round5/chain_pmc.txt).
 LBT_DEV float clip_q(const QState& s, float v) { return __builtin_amdgcn_fmed3f(v, -s.L, s.Lm1); }
 
 // v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: each half rounded exactly as the scalar op. The element
@@ -25,8 +26,10 @@ LBT_DEV pf2 pdiv(pf2 x, pf2 y, pf2 rc) {
   const pf2 r1 = __builtin_elementwise_fma(-y, q1, x);
   return __builtin_elementwise_copysign(__builtin_elementwise_fma(r1, rc, q1), x);
 }
-// pdiv for dividends that are never -0 (the copysign only restores x = -0; the BN normalisation's
-// q s - mu is q s for q = 0, i.e. +0, or a difference of two equal values, +0): one VALU fewer per element
+// pdiv for dividends that are never -0 (the copysign only restores div_fixup's -0 / y = -0; every other
+// quotient already carries x's sign): one VALU fewer per element. True of the BN differences it is used on:
+// x1 - mu with x1 = q * 2^-e (an integer code: +0 when q == 0) and t1 - t2 with t1 = G * 2^-e - mg (mg from
+// an integer sum: never -0), since a - b is -0 only when a is -0 and b is +0.
 LBT_DEV pf2 pdiv_nz(pf2 x, pf2 y, pf2 rc) {
   const pf2 q = x * rc;
   const pf2 r = __builtin_elementwise_fma(-y, q, x);

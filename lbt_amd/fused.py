@@ -901,16 +901,11 @@ class FusedResNet:
 
     @staticmethod
     def _bwd_tiles(d):
-        """lbt_conv_bwd_fused_i8's workgroup tiles for conv d (conv_mfma.hip tile_rows_for)."""
-        cs = d.Cin // 16
-        if cs != 1:
-            f23 = os.environ.get("LBT_TILE_ROWS23")
-            th = 2 if d.H % 4 == 0 and f23 != "4" and (f23 == "2" or d.N * d.H // 4 < 256) else 4
-        elif d.N * (d.H // 8) >= 256:
-            th = 8
-        else:
-            th = 2 if d.N * d.H // 4 < 256 else 4
-        return d.N * (d.H // th)
+        """lbt_conv_bwd_fused_i8's workgroup tiles for conv d (lbt_conv_fused_tile_rows, conv_fused_fwd.hip)."""
+        rows = _lib.load().lbt_conv_fused_tile_rows(d.Cin, d.N, d.H)
+        if rows <= 0:
+            raise _lib.LbtError("lbt_conv_fused_tile_rows(%d, %d, %d) = %d" % (d.Cin, d.N, d.H, rows))
+        return d.N * (d.H // rows)
 
     def _defers(self, d, fusable):
         """This conv's fused backward launch takes a deferred wgrad job (and defers its own)."""

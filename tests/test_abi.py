@@ -103,3 +103,27 @@ def test_host_side_argument_checks_return_einval():
     qx, qw = _lib.QDesc(), _lib.QDesc()
     qx.bits, qw.bits = 13, 2
     assert lib.lbt_conv_stem_wide_fwd(None, None, d, qx, qw, None, None) == 1001
+
+
+# (Cin, H, N) -> image rows per workgroup, from the rule of the fused conv launchers: the 16-channel stage
+# takes 8-row tiles while N * H / 8 >= 256, else 4-row tiles while N * H / 4 >= 256, else 2-row tiles; the
+# 32- / 64-channel stages 4-row tiles while N * H / 4 >= 256, else 2-row tiles.
+TILE_ROWS = [(16, 32, 128, 8), (16, 32, 64, 8), (16, 32, 32, 4), (16, 32, 16, 2), (32, 16, 128, 4), (32, 16, 32, 2),
+             (64, 8, 128, 4), (64, 8, 64, 2)]
+
+
+def test_conv_fused_tile_rows_table(monkeypatch):
+    """lbt_conv_fused_tile_rows (host only, nothing launched) under the default environment against the
+    table above, a negative status for an unsupported channel count, and FusedResNet._bwd_tiles == N * (H /
+    rows) for the same shapes."""
+    monkeypatch.delenv("LBT_TILE_ROWS1", raising=False)
+    monkeypatch.delenv("LBT_TILE_ROWS23", raising=False)
+    from lbt_amd.fused import FusedResNet
+    lib = _lib.load()
+    for Cin, H, N, rows in TILE_ROWS:
+        assert lib.lbt_conv_fused_tile_rows(Cin, N, H) == rows, (Cin, H, N)
+        W = 512 // Cin
+        d = _lib.ConvDesc(N, H, W, Cin, Cin, 3, 3, 1, 1, 1, 1, 1, 1, H, W)
+        assert FusedResNet._bwd_tiles(d) == N * (H // rows), (Cin, H, N)
+    for H, N in ((32, 128), (8, 1), (7, 1 << 20)):
+        assert lib.lbt_conv_fused_tile_rows(48, N, H) < 0

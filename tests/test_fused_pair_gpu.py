@@ -2,7 +2,7 @@
 
 conv_fwd_fused_kernel / conv_bwd_kernel run their phase-1 element chain only over the halo rows inside
 the image and the columns 0 .. W-1; the padding cells of the LDS halo image are filled by plain stores
-(conv_mfma.hip halo_pad_fill). At B = 2 .. 6 every stage takes 2-row tiles (tile_rows_for), so one
+(conv_fused.h halo_pad_fill). At B = 2 .. 6 every stage takes 2-row tiles (lbt_conv_fused_tile_rows), so one
 launch holds tiles at the top edge (no row above), in the middle and at the bottom edge (no row below)
 of one, two or three sample pairs, and an odd batch. The 4- and 8-row tiles run in
 test_gpu_parity.py's B = 32 .. 128 cases.

@@ -428,8 +428,8 @@ def test_fused_bench_workload_bitexact_vs_oracle(weight_bits, B):
     images, every fused kernel's W4 variant) against the oracle's 4-bit weight quantisers
     (dynamic_fixed_point.py:21-38 with bits=4). B=16 / 32: configs[2]'s per-GPU shards (global batch
     128 / 256 over 8 GPUs): the small-batch tile geometry (2-row tiles in every stage at B=16, 4-row
-    stage-1 and 2-row stage-2 / 3 tiles at B=32, 2-row stage-3 tiles only at B=64; conv_mfma.hip
-    tile_rows_for) and wgrad splits; (4, 16): the W4 variants of the 2-row tiles."""
+    stage-1 and 2-row stage-2 / 3 tiles at B=32, 2-row stage-3 tiles only at B=64; conv_fused_fwd.hip
+    lbt_conv_fused_tile_rows) and wgrad splits; (4, 16): the W4 variants of the 2-row tiles."""
     import bench
     from lbt_amd.fused import FusedResNet
     from lbt_amd.trainer import Trainer

@@ -1,6 +1,8 @@
-"""Per-kernel register / LDS / occupancy table of one .hip file (hipcc -Rpass-analysis).
+"""Per-kernel register / LDS / occupancy table of .hip files (hipcc -Rpass-analysis).
 
-    python tools/kres.py lbt_amd/csrc/conv_mfma.hip [name-filter]
+    python tools/kres.py lbt_amd/csrc/conv_fused_bwd.hip[,lbt_amd/csrc/conv_fused_fwd.hip,...] [name-filter]
+
+Without a name-filter every kernel is listed with its full argument list.
 """
 import os
 import re
@@ -13,10 +15,11 @@ from lbt_amd import _build  # noqa: E402
 
 
 def main():
-    src = sys.argv[1]
     filt = sys.argv[2] if len(sys.argv) > 2 else ""
-    cmd = [_build.HIPCC] + _build.FLAGS + ["-c", src, "-o", "/tmp/_kres.o", "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True).stderr
+    out = ""
+    for src in sys.argv[1].split(","):
+        cmd = [_build.HIPCC] + _build.FLAGS + ["-c", src, "-o", "/tmp/_kres.o", "-Rpass-analysis=kernel-resource-usage"]
+        out += subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None
     for line in out.splitlines():
         m = re.search(r"remark:\s+(.*?):\s+(.*?)\s+\[-Rpass", line)

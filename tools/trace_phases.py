@@ -72,7 +72,7 @@ def main():
         tr.step(xs[0], ys[0])
     torch.cuda.synchronize()
     lib = _lib.load()
-    setters = [getattr(lib, "lbt_trace_set_" + t) for t in ("conv", "bn", "head", "stem", "batched") if hasattr(lib, "lbt_trace_set_" + t)]
+    setters = [getattr(lib, "lbt_trace_set_" + t) for t in ("conv", "conv_bwd", "conv_fwd", "bn", "head", "stem", "batched") if hasattr(lib, "lbt_trace_set_" + t)]
     for s in setters:
         s.argtypes = [ctypes.c_void_p]
     nwg_max = 1 << 15
