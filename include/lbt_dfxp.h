@@ -513,6 +513,21 @@ int lbt_conv_wgrad_many_i8(const lbt_wgrad_job* jobs, int32_t njobs, void* strea
 int lbt_conv_wgrad_many_stem_i8(const lbt_wgrad_job* jobs, int32_t njobs, const lbt_chain_bwd_b* b, const int16_t* x,
                                 lbt_conv_desc d, int32_t* slab, int32_t nshard, void* stream);
 
+/* The batched launch's plan, host only (nothing is launched): the one definition of its rules, for the
+ * library and for whoever builds the job list.
+ * lbt_conv_wgrad_many_nsplit: the pixel splits (lbt_wgrad_job.nsplit) to give conv d's job. 3x3 convs of
+ * stride 1 (SAME) or 2 whose output rows tile 64-pixel chunks run the staged body: a split is 8 waves x
+ * chunks_per_wave chunks and divides the chunk count; other convs about tap_units workgroups (split x tap
+ * x co slice). 0 selects the default of either argument.
+ * lbt_conv_wgrad_many_blocks: the workgroups the launch gives that job at nsplit splits.
+ * lbt_conv_wgrad_many_slots: the workgroups of the launch that are resident at once on the current
+ * device (CUs x workgroups per CU). Negative: -LBT_EINVAL.
+ * Exactness: a wave's int32 accumulator sums at most 65536 pixels and a slab shard covers at most 65536
+ * pixels (|x * g| < 2^15); lbt_conv_wgrad_many_i8 rejects a job that breaks either.            */
+int lbt_conv_wgrad_many_nsplit(lbt_conv_desc d, int32_t chunks_per_wave, int32_t tap_units);
+int lbt_conv_wgrad_many_blocks(lbt_conv_desc d, int32_t nsplit);
+int lbt_conv_wgrad_many_slots(void);
+
 /* One stride-1 3x3 Conv2d_q's backward in ONE launch, with the BN backward passes on either side
  * (Conv2d_q.backward dynamic_fixed_point.py:299-305 between Normalization_q.backward :620-623 of
  * the BN it feeds and the BN it consumes):

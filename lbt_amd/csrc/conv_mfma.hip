@@ -25,6 +25,9 @@
 #include "lds_tr.h"
 #include "stem_bwd.h"
 
+#include <algorithm>
+#include <utility>
+
 using namespace lbt;
 
 namespace {
@@ -655,191 +658,267 @@ extern "C" int lbt_conv_wgrad_i8(const int8_t* xq, int32_t x_u8off, const int8_t
 // XCD-aware unit order). 3x3 / stride-1 / SAME jobs whose image rows tile 64-pixel chunks run
 // wgrad_s1_body, the others conv_wgrad_body (one unit = pixel split x tap x co slice).
 //
-// wgrad_s1_body: workgroup = (pixel split, ci slice, co slice) of kFW waves. A wave takes 64
-// consecutive output pixels at a time (whole image rows: 64 % W == 0, H % (64 / W) == 0), stages the
-// X slices of those rows plus a one-pixel halo ([64/W + 2][W + 2][16 B], the fill code outside the
-// image) and the 64 G slices in its own LDS region, and runs all 9 taps' MFMAs from there with
-// per-lane transposed reads: X and G leave L2 once per (ci, co) slice pair instead of once per tap,
-// and the next chunk's loads are in flight during the MFMAs. The waves' partials are summed in
-// LDS and added into the job's slab (shard = split % nshard) with one integer atomic per output.
+// wgrad_s1_body<NCO, NH>: workgroup = (pixel split, ci slice, group of NCO co slices) of kFW waves. A
+// wave takes 64 consecutive output pixels at a time (whole image rows: 64 % W == 0, H % (64 / W) == 0)
+// and stages, by LDS-DMA into its own ring of kWgmBufs buffers, the X slices of those rows plus a
+// one-pixel halo ([64/W + 2][W + 2][16 B] in NH pieces of 64 slices, the fill code outside the image)
+// and the pixels' NCO * 16 contiguous G bytes; all 9 * NCO MFMAs run from that image with per-lane
+// transposed reads. X leaves L2 once per (ci slice, co group) and G once per ci slice instead of once
+// per (ci, co) slice pair, and the LDS image and the wave-uniform chunk arithmetic are paid once for
+// 9 * NCO MFMAs. The staging holds no registers, which is what leaves room for the 36 * NCO accumulator
+// registers at two workgroups per CU. The waves' partials are summed in LDS, one co slice at a time,
+// and added into the job's slab (shard = split % nshard) with one integer atomic per output.
+// Exactness: an int32 accumulator of a wave sums at most 65536 pixels and a slab shard covers at most
+// 65536 pixels (|x * g| <= 255 * 128 < 2^15); both are checked on the host (wgrad_setup,
+// wgrad_s1_variant). The sums are integers, so any split and any order give the same slab totals.
 namespace {
 constexpr int kMaxWJobs = 24;
-#ifndef LBT_WGM_OCC
-#define LBT_WGM_OCC 4  // waves per SIMD the batched launch's registers are budgeted for
-#endif
-#ifndef LBT_WGM_BUFS
-#define LBT_WGM_BUFS 2
-#endif
-#ifndef LBT_WGX
-#define LBT_WGX 0
-#endif
-constexpr int kWgmBufs = LBT_WGM_BUFS;  // chunks of loads in flight per wave (register buffers)
+constexpr int kWgmOcc = 4;    // waves per SIMD the batched launch's registers are budgeted for: 2 workgroups per CU
+constexpr int kWgmBufs = 2;   // chunks in flight per wave (LDS-DMA ring)
+constexpr int kWgmBuf = 4096; // bytes of one ring buffer: NH KB of X halo slices | NCO KB of G
 constexpr int kFW = 8;        // waves per workgroup of the batched launch
-constexpr int kHaloMax = 3;   // halo slices per lane: (64/W + 2) * (W + 2) <= 192 (W | 64, 2 <= W <= 32)
+// The plan's defaults (lbt_conv_wgrad_many_nsplit): at 128 images the ResNet-20 launch, the stem's 256
+// workgroups included, then has fewer workgroups than are resident at once (2 per CU), so none waits for
+// another to end; a workgroup costs about 10 us whatever its share of the work
+constexpr int kWgmCpw = 16;        // default 64-pixel chunks per wave of a staged job
+constexpr int kWgmMinUnits = 8;    // workgroups per staged job, at least (while a wave keeps one chunk)
+constexpr int kWgmTapUnits = 16;   // workgroups per per-tap job, about
+constexpr int kHaloMax = 3;   // halo pieces per chunk of the stride-1 instances: (64/W + 2) * (W + 2) <= 192
 struct WgradMany {
   WgradArgs j[kMaxWJobs];
   uint32_t start[kMaxWJobs + 1];
-  int32_t fast[kMaxWJobs];
+  int32_t fast[kMaxWJobs];  // 0: conv_wgrad_body; else wgrad_s1_variant
   int n;
 };
 union WgradManyShared {
   WgradShared<1, kFW> s1;
   WgradShared<2, kFW> s2;
-  int8_t stage[kFW][5 * 1024];               // wgrad_s1_body: per wave X halo | G (at +4096)
-  // wgrad_s1_body: partials [tap][kg][r][4] of wave pair (w, w + kFW/2), summed in place (the LDS of
-  // three workgroups per CU: the batched launch fits one round)
+  int8_t stage[kFW][kWgmBufs * kWgmBuf];     // wgrad_s1_body: per wave the ring of X halo | G images
+  // wgrad_s1_body: partials [tap][kg][r][4] of wave pair (w, w + kFW/2), summed in place, one co slice
+  // at a time (both slices at once need 72 KB: measured 2.7 us slower, the launch no longer keeps two
+  // workgroups per CU)
   int red[kFW / 2][9 * 256];
 };
 
-bool wgrad_s1_ok(const lbt_conv_desc& d, int nsplit) {
-  if (d.KH != 3 || d.KW != 3 || d.SH != 1 || d.SW != 1 || d.PT != 1 || d.PB != 1 || d.PL != 1 || d.PR != 1 ||
-      d.Ho != d.H || d.Wo != d.W || d.W > 64 || 64 % d.W || d.H % (64 / d.W) ||
-      (64 / d.W + 2) * (d.W + 2) > 64 * kHaloMax)
-    return false;
-  const int64_t chunks = (int64_t)d.N * d.H * d.W / 64;
-  return nsplit > 0 && chunks % nsplit == 0;
+// The staged body's instance for this conv and split: 0 none (conv_wgrad_body takes it), else
+// 1 <NCO 1, NH 3>, 2 <NCO 1, NH 2>, 3 <NCO 2, NH 2> (3x3 / 1 SAME; one ring buffer holds NH + NCO <= 4 KB),
+// 4 <NCO 2, NH 5, stride 2, one buffer> (3x3 / 2)
+int wgrad_s1_variant(const lbt_conv_desc& d, int nsplit) {
+  if (d.KH != 3 || d.KW != 3 || d.SH != d.SW || (d.SH != 1 && d.SH != 2) || d.PT < 0 || d.PT > 1 || d.PL < 0 ||
+      d.PL > 1 || d.Wo <= 0 || d.Wo > 64 || 64 % d.Wo || d.Ho % (64 / d.Wo))
+    return 0;
+  if (d.SH == 1 && (d.PT != 1 || d.PB != 1 || d.PL != 1 || d.PR != 1 || d.Ho != d.H || d.Wo != d.W)) return 0;
+  const int64_t chunks = (int64_t)d.N * d.Ho * d.Wo / 64;
+  if (nsplit <= 0 || chunks % nsplit) return 0;
+  // a wave walks ceil(chunks per split / kFW) chunks of 64 pixels: at most 65536 pixels per accumulator
+  if ((chunks / nsplit + kFW - 1) / kFW * 64 > 65536) return 0;
+  const int nhalo = ((64 / d.Wo - 1) * d.SH + 3) * ((d.Wo - 1) * d.SH + 3), nh = (nhalo + 63) / 64;
+  const bool co2 = (d.Cout / 16) % 2 == 0;
+  if (d.SH == 2) return (co2 && nh <= 5) ? 4 : 0;
+  if (nh > kHaloMax) return 0;
+  if (nh == 3) return 1;
+  return co2 ? 3 : 2;
 }
+int wgrad_s1_nco(int variant) { return variant >= 3 ? 2 : 1; }
 
-LBT_DEV v4i tr_frag_at(const int8_t* img, int oa, int ob) {
-  typedef __attribute__((address_space(3))) v2i lds_v2i;
-  const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i*)(img + oa));
-  const v2i hi = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i*)(img + ob));
+static __device__ __attribute__((aligned(16))) uint32_t kWgFill80[4] = {0x80808080u, 0x80808080u, 0x80808080u,
+                                                                        0x80808080u};
+typedef __attribute__((address_space(3))) void* wg_lds_vptr;
+template <int N>
+LBT_DEV void wg_vm_wait() {
+  static_assert(N >= 0 && N < 64, "vmcnt");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// ds_read_b64_tr_b8 as inline asm: the compiler's waitcnt pass makes every ds_read_tr intrinsic wait
+// for ALL outstanding LDS-DMA (vmcnt(0): it cannot tell the ring's buffers apart), which would
+// serialise the ring. The asm form is invisible to it, so its results are fenced by hand (wg_tr_wait:
+// s_waitcnt lgkmcnt(0) taking the fragments as in/out operands, so no use moves above it).
+template <int OFF>
+LBT_DEV v4i wg_tr_frag(uint32_t a, uint32_t b) {
+  v2i lo, hi;
+  asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(lo) : "v"(a), "n"(OFF) : "memory");
+  asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(hi) : "v"(b), "n"(OFF) : "memory");
   return v4i{lo.x, lo.y, hi.x, hi.y};
 }
+LBT_DEV void wg_tr_wait(v4i& a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)::"memory"); }
+LBT_DEV void wg_tr_wait(v4i& a, v4i& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory"); }
+LBT_DEV void wg_tr_wait(v4i& a, v4i& b, v4i& c) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c)::"memory");
+}
 
+template <int I>
+using wg_int = std::integral_constant<int, I>;
+template <class F, int... I>
+LBT_DEV void wg_static_for(F&& f, std::integer_sequence<int, I...>) {
+  (f(wg_int<I>{}), ...);
+}
+
+template <int NCO, int NH, int S = 1, int NB = kWgmBufs>
 __device__ __forceinline__ void wgrad_s1_body(const WgradArgs& wa, uint32_t bid, WgradManyShared& sm) {
+  constexpr int kBuf = kWgmBufs * kWgmBuf / NB;  // bytes of one of this instance's NB buffers
+  static_assert((NH + NCO) * 1024 <= kBuf && (NB == 1 || NB == kWgmBufs), "one ring buffer");
   const lbt_conv_desc& d = wa.d;
-  const int H = d.H, W = d.W, Cin = d.Cin, Cout = d.Cout;
-  const int ncs = Cin >> 4, ncos = Cout >> 4, nsplit = wa.nsplit;
-  const int total = nsplit * ncs * ncos;
+  const int H = d.H, W = d.W, Wo = d.Wo, Cin = d.Cin, Cout = d.Cout;
+  const int ncs = Cin >> 4, ncog = (Cout >> 4) / NCO, nsplit = wa.nsplit;
+  const int total = nsplit * ncs * ncog;
   const int xchunk = (total + 7) >> 3;
   const int u = (int)(bid & 7) * xchunk + (int)(bid >> 3);  // XCD-aware: a split's slices share an L2
   if (u >= total) return;
-  const int split = u / (ncs * ncos), urem = u - split * (ncs * ncos);
-  const int cis = urem / ncos, cos = urem - cis * ncos;
+  const int split = u / (ncs * ncog), urem = u - split * (ncs * ncog);
+  const int cis = urem / ncog, cog = urem - cis * ncog;
   const int lane = threadIdx.x & 63, wave = wave_id();
   const int j = lane & 15, kg = lane >> 4;
-  const int RB = 64 / W, Wp = W + 2, nhalo = (RB + 2) * Wp;
-  const int64_t cps = (int64_t)d.N * H * W / 64 / nsplit;  // chunks per split (exact: host check)
-  const int64_t c0 = (int64_t)split * cps;
-  const int nmine = cps > wave ? (int)((cps - wave + kFW - 1) / kFW) : 0;
-  const int HW = H * W;
-  const int fill = wa.x_fill;
-  int8_t* st = sm.stage[wave];
-  int8_t* gs = st + 4096;
-  // per-lane transposed-read offsets (chunk-invariant): pixels pa = 16kg + j/2 and pa + 8
+  // a chunk = RB whole output rows; its input window = WR rows x Wp columns from input pixel
+  // (S * first output row - PT, -PL)
+  const int RB = 64 / Wo, WR = (RB - 1) * S + 3, Wp = (Wo - 1) * S + 3, nhalo = WR * Wp;
+  const int bpi = d.Ho / RB;                                // chunks (row blocks) per image
+  const int cps = (int)((int64_t)d.N * bpi / nsplit);       // chunks per split (exact: host check)
+  const int c0 = split * cps;
+  const int nmine = cps > wave ? (cps - wave + kFW - 1) / kFW : 0;
+  const int8_t* xfill = wa.x_fill ? reinterpret_cast<const int8_t*>(kWgFill80) : reinterpret_cast<const int8_t*>(zi());
+  const int8_t* zero = reinterpret_cast<const int8_t*>(zi());
+  int8_t* region = sm.stage[wave];
+  typedef __attribute__((address_space(3))) int8_t wg_lds_i8;
+  const uint32_t rbase = (uint32_t)(uintptr_t)(wg_lds_i8*)region;  // LDS byte address of this wave's ring
+  // per-lane transposed-read addresses in ring buffer 0 (chunk-invariant): pixels pa = 16kg + j/2 and
+  // pa + 8; X by kernel row (the tap's column and the ring buffer are immediate offsets), G slice 0
   const int pa = 16 * kg + (j >> 1), pb = pa + 8;
-  const int oxa = ((pa / W) * Wp + pa % W) * 16 + 8 * (j & 1);
-  const int oxb = ((pb / W) * Wp + pb % W) * 16 + 8 * (j & 1);
-  const int oga = pa * 16 + 8 * (j & 1), ogb = pb * 16 + 8 * (j & 1);
-  // chunk-invariant geometry of this lane's halo slices t = lane + 64 i of the [RB + 2][W + 2] window:
-  // the offset from the chunk's first pixel, whether it is a real column inside the window, whether it
-  // lies in the window's top / bottom row (outside the image at the first / last row block). The
-  // per-chunk part is then wave-uniform (scalar): the per-lane divisions by W + 2 of every chunk were
-  // most of the loop's VALU instructions
-  int hoff[kHaloMax];
+  uint32_t xa[3], xb[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    xa[r] = rbase + (uint32_t)((((pa / Wo) * S + r) * Wp + (pa % Wo) * S) * 16 + 8 * (j & 1));
+    xb[r] = rbase + (uint32_t)((((pb / Wo) * S + r) * Wp + (pb % Wo) * S) * 16 + 8 * (j & 1));
+  }
+  const uint32_t ga = rbase + (uint32_t)(NH * 1024 + pa * 16 * NCO + 8 * (j & 1));
+  const uint32_t gb = rbase + (uint32_t)(NH * 1024 + pb * 16 * NCO + 8 * (j & 1));
+  // chunk-invariant geometry of this lane's halo slices t = lane + 64 i of the [WR][Wp] window: the
+  // offset from input pixel (S * first output row, 0), whether it is a real column inside the window,
+  // whether it lies in a window row above the image at the first row block / below it at the last; and of
+  // its G pieces q = lane + 64 c of the chunk's [64 px][NCO][16 B] block. The per-chunk part is wave-uniform.
+  const int hbot0 = H - (d.Ho - RB) * S + d.PT;  // window rows >= this are below the image at the last row block
+  int hoff[NH], goff[NCO];
   uint32_t hin = 0, htop = 0, hbot = 0;
 #pragma unroll
-  for (int i = 0; i < kHaloMax; ++i) {
+  for (int i = 0; i < NH; ++i) {
     const int t = lane + 64 * i;
     const int hy = t / Wp, hx = t - hy * Wp;
-    hoff[i] = ((hy - 1) * W + hx - 1) * Cin;
-    hin |= (uint32_t)(t < nhalo && hx >= 1 && hx <= W) << i;
-    htop |= (uint32_t)(hy == 0) << i;
-    hbot |= (uint32_t)(hy == RB + 1) << i;
+    hoff[i] = ((hy - d.PT) * W + hx - d.PL) * Cin;
+    hin |= (uint32_t)(t < nhalo && hx >= d.PL && hx < W + d.PL) << i;
+    htop |= (uint32_t)(hy < d.PT) << i;
+    hbot |= (uint32_t)(hy >= hbot0) << i;
   }
+#pragma unroll
+  for (int c = 0; c < NCO; ++c) {
+    const int q = lane + 64 * c;
+    goff[c] = (q / NCO) * Cout + (cog * NCO + q % NCO) * 16;
+  }
+  v4i acc[9][NCO];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) acc[t][c] = v4i{0, 0, 0, 0};
 
-  // two register buffers: chunk s + 2's loads are issued while chunk s is computed (s + 1's are
-  // already in flight), so a wave waits on a load issued two chunks earlier
-  struct Buf {
-    v4i x[kHaloMax], g;
-    uint32_t valid;
-  };
-  auto load = [&](Buf& b, int64_t c) {
-    const int64_t p0 = c * 64;  // wave-uniform: the chunk's first pixel, RB whole rows of image n
-    const int n = (int)(p0 / HW), row0 = (int)(p0 - (int64_t)n * HW) / W;
-    const int8_t* xim = wa.xq + (p0 * Cin + cis * 16);  // = pixel (n, row0, 0)
-    b.valid = hin & ~(row0 == 0 ? htop : 0u) & ~(row0 + RB == H ? hbot : 0u);
+  // The wave's chunks are c0 + wave + kFW s, s < nmine; issue() is called for s = 0, 1, 2, ... in order
+  // and carries the chunk, its image and its row block within the image along (no division per chunk).
+  // A step past the end re-stages the last chunk's X with zero G: every DMA is unconditional, so the
+  // counted vmcnt waits below are exact.
+  constexpr int kDma = NH + NCO;  // DMA instructions per chunk
+  int ic = c0 + wave, in = ic / bpi, im = ic - in * bpi;
+  const int instep = kFW / bpi, imstep = kFW - instep * bpi;
+  auto issue = [&](int k, int s) {
+    // wave-uniform: the chunk's first output pixel and its window's origin row, RB whole rows of image in
+    const int64_t p0 = (int64_t)ic * 64, x0 = ((int64_t)in * H + im * (RB * S)) * W;
+    const int8_t* xim = wa.xq + (x0 * Cin + cis * 16);
+    const uint32_t valid = hin & ~(im == 0 ? htop : 0u) & ~(im == bpi - 1 ? hbot : 0u);
+    int8_t* b = region + k * kBuf;
 #pragma unroll
-    for (int i = 0; i < kHaloMax; ++i)
-      b.x[i] = *reinterpret_cast<const v4i*>(xim + ((b.valid >> i) & 1 ? hoff[i] : 0));
-    b.g = *reinterpret_cast<const v4i*>(wa.gq + (p0 + lane) * Cout + cos * 16);
-  };
-  v4i acc[9];
+    for (int i = 0; i < NH; ++i)
+      __builtin_amdgcn_global_load_lds((valid >> i) & 1 ? xim + hoff[i] : xfill, (wg_lds_vptr)(b + i * 1024), 16, 0, 0);
+    const int8_t* gim = wa.gq + p0 * Cout;
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = v4i{0, 0, 0, 0};
-  // this wave's chunk s, clamped to its last one: the refills past the end reload it and every load
-  // is UNCONDITIONAL, so the compiler's vmcnt waits count exactly the loads issued since (a load
-  // under a branch made it wait for vmcnt(0) -- every chunk then paid a whole memory round trip:
-  // 8 chunks ~ 12 us per stage-1 job, tools/trace_phases.py, profiles/round6/budget)
-  auto cidx = [&](int s) { return c0 + wave + (int64_t)(s < nmine ? s : nmine - 1) * kFW; };
-  // chunk s of this wave: stage b into LDS, refill b with chunk s + kWgmBufs, MFMAs of all 9 taps
-  // (a step past the end, s >= nmine, adds a zero gradient fragment)
-  // LBT_WGX (scratch timing builds only, wrong results): 1 no refill loads, 2 no LDS staging stores,
-  // 4 no transposed LDS reads (register operands), 8 no MFMAs (integer adds)
-  auto step = [&](Buf& b, int s) {
-    if constexpr (!(LBT_WGX & 2)) {
-#pragma unroll
-      for (int i = 0; i < kHaloMax; ++i) {
-        const int t = lane + 64 * i;
-        const v4i v = (b.valid >> i) & 1 ? b.x[i] : v4i{fill, fill, fill, fill};
-        if (t < nhalo) *reinterpret_cast<v4i*>(st + t * 16) = v;
+    for (int c = 0; c < NCO; ++c)
+      __builtin_amdgcn_global_load_lds(s < nmine ? gim + goff[c] : zero, (wg_lds_vptr)(b + (NH + c) * 1024), 16, 0, 0);
+    if (s + 1 < nmine) {
+      ic += kFW;
+      in += instep;
+      im += imstep;
+      if (im >= bpi) {
+        im -= bpi;
+        ++in;
       }
-      *reinterpret_cast<v4i*>(gs + lane * 16) = s < nmine ? b.g : v4i{0, 0, 0, 0};
     }
-    // the images are read by other lanes of the same wave only: a wave's LDS instructions execute in
-    // issue order, so only the compiler must keep the reads after the writes (no fence: a workgroup
-    // release fence would also wait for the refills in flight)
-    asm volatile("" ::: "memory");
-    if constexpr (!(LBT_WGX & 1)) load(b, cidx(s + kWgmBufs));
-    const v4i bfrag = (LBT_WGX & 4) ? b.g : tr_frag_at(gs, oga, ogb);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int toff = ((t / 3) * Wp + t % 3) * 16;
-      const v4i afrag = (LBT_WGX & 4) ? b.x[t % kHaloMax] : tr_frag_at(st, oxa + toff, oxb + toff);
-      if constexpr (LBT_WGX & 8)
-        acc[t] = acc[t] + afrag + bfrag;
-      else
-        acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(afrag, bfrag, acc[t], 0, 0, 0);
-    }
-    asm volatile("" ::: "memory");  // the next chunk's stores after these reads (in-order LDS)
   };
   LBT_TS(0);
-  if (nmine > 0) {  // kWgmBufs register buffers: chunk s + kWgmBufs's loads issued during chunk s
-    Buf bf[kWgmBufs];
+  if (nmine > 0) {  // NB == 1: one chunk at a time (the strided instance's window takes the whole region)
+    if constexpr (NB > 1) {
 #pragma unroll
-    for (int k = 0; k < kWgmBufs; ++k) load(bf[k], cidx(k));
-    for (int s = 0; s < nmine; s += kWgmBufs) {
-#pragma unroll
-      for (int k = 0; k < kWgmBufs; ++k) step(bf[k], s + k);
+      for (int k = 0; k < NB; ++k) issue(k, k);
     }
+    for (int s = 0; s < nmine; s += NB) {
+      wg_static_for(
+          [&](auto K) {
+            constexpr int k = decltype(K)::value, kb = k * kBuf;
+            if constexpr (NB == 1) issue(0, s);
+            wg_vm_wait<(NB - 1) * kDma>();  // chunk s + k landed; the younger chunk may be in flight
+            v4i bf[NCO];
+            wg_static_for([&](auto C) { bf[decltype(C)::value] = wg_tr_frag<kb + decltype(C)::value * 16>(ga, gb); },
+                          std::make_integer_sequence<int, NCO>{});
+            v4i af = wg_tr_frag<kb>(xa[0], xb[0]);
+            if constexpr (NCO == 2)
+              wg_tr_wait(bf[0], bf[1], af);
+            else
+              wg_tr_wait(bf[0], af);
+            wg_static_for(
+                [&](auto T) {  // tap t + 1's fragment is read under tap t's MFMAs
+                  constexpr int t = decltype(T)::value;
+                  v4i an = af;
+                  if constexpr (t < 8) an = wg_tr_frag<kb + ((t + 1) % 3) * 16>(xa[(t + 1) / 3], xb[(t + 1) / 3]);
+#pragma unroll
+                  for (int c = 0; c < NCO; ++c)
+                    acc[t][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf[c], acc[t][c], 0, 0, 0);
+                  if constexpr (t < 8) {
+                    wg_tr_wait(an);
+                    af = an;
+                  }
+                },
+                std::make_integer_sequence<int, 9>{});
+            if constexpr (NB > 1) issue(k, s + k + NB);  // this buffer's reads are done (the last wg_tr_wait)
+          },
+          std::make_integer_sequence<int, NB>{});
+    }
+    wg_vm_wait<0>();  // the trailing (clamped) DMAs: nothing may still write LDS past here
   }
   LBT_TS(1);
-  __syncthreads();  // the partials overwrite the staging regions
-  // acc[t] element i: ci = 4kg + i, co = j (16x16 C/D map); waves w and w + kFW/2 share slot w
+  // acc[t][c] element i: ci = 4kg + i, co = j of co slice cog * NCO + c (16x16 C/D map); waves w and
+  // w + kFW/2 share slot w; one co slice at a time
   constexpr int kHalf = kFW / 2;
-  if (wave < kHalf) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t) *reinterpret_cast<v4i*>(&sm.red[wave][(t * 64 + lane) * 4]) = acc[t];
-  }
-  __syncthreads();
-  if (wave >= kHalf) {
+  for (int c = 0; c < NCO; ++c) {
+    __syncthreads();  // the partials overwrite the staging regions / the previous slice's partials
+    if (wave < kHalf) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      v4i* q = reinterpret_cast<v4i*>(&sm.red[wave - kHalf][(t * 64 + lane) * 4]);
-      *q = *q + acc[t];
+      for (int t = 0; t < 9; ++t) *reinterpret_cast<v4i*>(&sm.red[wave][(t * 64 + lane) * 4]) = acc[t][c];
     }
-  }
-  __syncthreads();
-  LBT_TS(2);
-  int32_t* dst = wa.slab + (int64_t)(split % wa.nshard) * 9 * Cin * Cout + (int64_t)cis * 16 * Cout + cos * 16;
-  for (int i = threadIdx.x; i < 9 * 256; i += kFW * 64) {
-    int v = 0;
+    __syncthreads();
+    if (wave >= kHalf) {
 #pragma unroll
-    for (int w = 0; w < kHalf; ++w) v += sm.red[w][i];
-    const int t = i >> 8, l = (i >> 2) & 63, ii = i & 3;
-    const int ci = 4 * (l >> 4) + ii, co = l & 15;
-    if (v) LBT_GADD(&dst[((int64_t)t * Cin + ci) * Cout + co], v);  // integer atomics: exact, order-independent
+      for (int t = 0; t < 9; ++t) {
+        v4i* q = reinterpret_cast<v4i*>(&sm.red[wave - kHalf][(t * 64 + lane) * 4]);
+        *q = *q + acc[t][c];
+      }
+    }
+    __syncthreads();
+    if (c == 0) LBT_TS(2);
+    int32_t* dst = wa.slab + (int64_t)(split % wa.nshard) * 9 * Cin * Cout + (int64_t)cis * 16 * Cout +
+                   (cog * NCO + c) * 16;
+    for (int i = threadIdx.x; i < 9 * 256; i += kFW * 64) {
+      int v = 0;
+#pragma unroll
+      for (int w = 0; w < kHalf; ++w) v += sm.red[w][i];
+      const int t = i >> 8, l = (i >> 2) & 63, ii = i & 3;
+      const int ci = 4 * (l >> 4) + ii, co = l & 15;
+      if (v) LBT_GADD(&dst[((int64_t)t * Cin + ci) * Cout + co], v);  // integer atomics: exact, order-independent
+    }
   }
   LBT_TS(3);
 }
@@ -854,9 +933,12 @@ LBT_DEV void wgrad_many_block(const WgradMany& m, uint32_t b, WgradManyShared& s
 #ifdef LBT_TRACE
   if (threadIdx.x == 0 && lbt_trace_buf) lbt_trace_buf[(size_t)blockIdx.x * 8 + 6] = (unsigned long long)(j + 1);
 #endif
-  if (m.fast[j]) {
-    wgrad_s1_body(wa, rb, sm);
-    return;
+  switch (m.fast[j]) {  // wgrad_s1_variant
+    case 1: wgrad_s1_body<1, 3>(wa, rb, sm); return;
+    case 2: wgrad_s1_body<1, 2>(wa, rb, sm); return;
+    case 3: wgrad_s1_body<2, 2>(wa, rb, sm); return;
+    case 4: wgrad_s1_body<2, 5, 2, 1>(wa, rb, sm); return;
+    default: break;
   }
   switch (wa.d.Cin >> 4) {
     case 1: conv_wgrad_body<1, kFW>(wa, rb, sm.s1); break;
@@ -864,7 +946,7 @@ LBT_DEV void wgrad_many_block(const WgradMany& m, uint32_t b, WgradManyShared& s
   }
 }
 
-__global__ __launch_bounds__(kFW * 64, LBT_WGM_OCC) void conv_wgrad_many_kernel(const WgradMany m) {
+__global__ __launch_bounds__(kFW * 64, kWgmOcc) void conv_wgrad_many_kernel(const WgradMany m) {
   __shared__ __attribute__((aligned(16))) WgradManyShared sm;
   wgrad_many_block(m, blockIdx.x, sm);
 }
@@ -880,7 +962,7 @@ union WgradManyStemShared {
 };
 static_assert(kFW * 64 == 2 * 256, "two stem row blocks per workgroup of the batched launch");
 // (stem_first, the default: the stem's workgroups are the launch's FIRST blocks; else its last)
-__global__ __launch_bounds__(kFW * 64, LBT_WGM_OCC) void conv_wgrad_many_stem_kernel(const WgradMany m,
+__global__ __launch_bounds__(kFW * 64, kWgmOcc) void conv_wgrad_many_stem_kernel(const WgradMany m,
                                                                                     const StemBwdArgs st,
                                                                                     uint32_t pairs, int stem_first) {
   __shared__ __attribute__((aligned(16))) WgradManyStemShared sm;
@@ -899,9 +981,9 @@ int wgrad_many_setup(const lbt_wgrad_job& w, WgradArgs& wa, uint32_t& blocks, in
   if (!w.slab || !w.xq || !w.gq) return LBT_EINVAL;
   const int e = wgrad_setup(w.xq, w.x_u8off, w.gq, w.d, w.slab, w.nsplit, w.nshard, wa, blocks);
   if (e) return e;
-  fast = wgrad_s1_ok(w.d, w.nsplit) ? 1 : 0;
+  fast = wgrad_s1_variant(w.d, w.nsplit);
   if (fast) {
-    const int64_t units = (int64_t)w.nsplit * (w.d.Cin / 16) * (w.d.Cout / 16);
+    const int64_t units = (int64_t)w.nsplit * (w.d.Cin / 16) * (w.d.Cout / 16 / wgrad_s1_nco(fast));
     blocks = (uint32_t)((units + 7) / 8 * 8);
   } else if (w.d.Cin != 16 && w.d.Cin != 32) {
     return LBT_EINVAL;  // conv_wgrad_body<CSI, kFW> instances: CSI 1, 2
@@ -909,6 +991,57 @@ int wgrad_many_setup(const lbt_wgrad_job& w, WgradArgs& wa, uint32_t& blocks, in
   return 0;
 }
 }  // namespace
+
+// ---- the batched launch's plan: one host-only definition for the library and the Python planner.
+// Resident workgroups of the batched launch: CUs x the kFW-wave workgroups that kWgmOcc waves per
+// SIMD admit (the kernels' launch bounds; registers and LDS both allow exactly that: tools/kres.py).
+extern "C" int lbt_conv_wgrad_many_slots(void) {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;  // MI355X
+    return n;
+  }();
+  return cus * (kWgmOcc * 4 / kFW);
+}
+
+// Workgroups of conv d's job at nsplit pixel splits (a multiple of 8), -LBT_EINVAL for a job the launch
+// does not take.
+extern "C" int lbt_conv_wgrad_many_blocks(lbt_conv_desc d, int32_t nsplit) {
+  if (!desc_ok(d) || d.Cin % 16 || d.Cout % 16 || nsplit <= 0) return -LBT_EINVAL;
+  const int v = wgrad_s1_variant(d, nsplit);
+  if (!v && d.Cin != 16 && d.Cin != 32) return -LBT_EINVAL;
+  const int64_t units = v ? (int64_t)nsplit * (d.Cin / 16) * (d.Cout / 16 / wgrad_s1_nco(v))
+                          : (int64_t)nsplit * d.KH * d.KW * (d.Cout / 16);
+  return units < ((int64_t)1 << 30) ? (int)((units + 7) / 8 * 8) : -LBT_EINVAL;
+}
+
+// Pixel splits of conv d's job. Staged instances (wgrad_s1_variant): a split is kFW waves x
+// chunks_per_wave 64-pixel chunks, rounded down to a divisor of the chunk count; per-tap jobs:
+// about tap_units workgroups (split x tap x co slice) of at least 512 pixels. 0 selects the default
+// of either argument.
+extern "C" int lbt_conv_wgrad_many_nsplit(lbt_conv_desc d, int32_t chunks_per_wave, int32_t tap_units) {
+  if (!desc_ok(d) || d.Cin % 16 || d.Cout % 16) return -LBT_EINVAL;
+  const int64_t P = (int64_t)d.N * d.Ho * d.Wo;
+  const int v = wgrad_s1_variant(d, 1);
+  if (!v) {
+    const int64_t lo = (P + 65535) / 65536, taps = (int64_t)d.KH * d.KW * (d.Cout / 16);
+    const int64_t want = std::max<int64_t>(1, (tap_units > 0 ? tap_units : kWgmTapUnits) / taps);
+    return (int)std::max(lo, std::min(want, std::max<int64_t>(1, P / 512)));
+  }
+  const int64_t chunks = P / 64, units = (int64_t)(d.Cin / 16) * (d.Cout / 16 / wgrad_s1_nco(v));
+  const int cpw = chunks_per_wave > 0 ? chunks_per_wave : kWgmCpw;
+  int64_t ns = std::max<int64_t>(1, chunks / ((int64_t)kFW * cpw));
+  if (chunks_per_wave <= 0) {
+    // small batches: more, shorter splits (down to one chunk per wave) until the job has kWgmMinUnits
+    // workgroups -- a job takes as long as one workgroup's serial chunk loop
+    while (ns * units < kWgmMinUnits && 2 * ns * kFW <= chunks) ns *= 2;
+  }
+  ns = std::max(ns, (chunks + kFW * 1024 - 1) / (kFW * 1024));  // <= 65536 pixels per wave
+  while (chunks % ns) --ns;
+  return (int)ns;
+}
 
 extern "C" int lbt_conv_wgrad_many_i8(const lbt_wgrad_job* jobs, int32_t njobs, void* stream) {
   if (njobs < 0 || (njobs > 0 && !jobs)) return LBT_EINVAL;

@@ -197,39 +197,27 @@ def wgrad_nsplit(d, generic=False):
     return max(lo, min(want, max(1, P // 512)))
 
 
-def wgrad_s1_ok(d):
-    """lbt_conv_wgrad_many_i8's staged 3x3 / stride-1 body takes this conv (64-pixel chunks of
-    whole image rows); mirrors wgrad_s1_ok in conv_mfma.hip."""
-    return (d.KH == 3 and d.KW == 3 and d.SH == 1 and d.SW == 1 and d.PT == 1 and d.PB == 1 and d.PL == 1
-            and d.PR == 1 and d.Ho == d.H and d.Wo == d.W and d.W <= 64 and 64 % d.W == 0
-            and d.H % (64 // d.W) == 0 and (64 // d.W + 2) * (d.W + 2) <= 192)
-
-
-WGRAD_CPW = int(os.environ.get("LBT_WGRAD_CPW", "8"))  # batched staged wgrad: 64-pixel chunks per wave
-WGRAD_MIN_UNITS = int(os.environ.get("LBT_WGRAD_MIN_UNITS", "32"))  # batched staged wgrad: workgroups per job, at least
-WGRAD_UNITS = int(os.environ.get("LBT_WGRAD_UNITS", "64"))  # batched per-tap wgrad: workgroups per conv (sweep: 32 / 48 / 64 / 80 / 96 / 128 -> 49 / 30 / 26 / 29 / 29 / 30 us)
+WGRAD_CPW = int(os.environ.get("LBT_WGRAD_CPW", "0"))  # batched staged wgrad: 64-pixel chunks per wave (0: the library's default)
+WGRAD_UNITS = int(os.environ.get("LBT_WGRAD_UNITS", "0"))  # batched per-tap wgrad: workgroups per conv (0: the library's default)
 
 
 def wgrad_nsplit_batched(d, chunks_per_wave=None):
-    """Pixel splits of a conv's wgrad inside the batched launch (8-wave workgroups). Staged 3x3
-    body: each split = 8 waves x `chunks_per_wave` 64-pixel chunks, a divisor of the chunk count.
-    Other convs: ~128 workgroups (split x tap x co slice) per conv."""
-    P = d.N * d.Ho * d.Wo
-    if wgrad_s1_ok(d):
-        chunks = P // 64
-        ns = max(1, chunks // (8 * (chunks_per_wave or WGRAD_CPW)))
-        if chunks_per_wave is None:
-            # small batches: more, shorter splits (down to one chunk per wave) until the job has
-            # WGRAD_MIN_UNITS workgroups -- a job takes as long as one workgroup's serial chunk loop, so
-            # at 16 images per GPU 8 chunks per wave left the launch at 8-16 workgroups (B=128: unchanged)
-            units = (d.Cin // 16) * (d.Cout // 16)
-            while ns * units < WGRAD_MIN_UNITS and 2 * ns * 8 <= chunks:
-                ns *= 2
-        while chunks % ns:
-            ns -= 1
-        return ns
-    lo = -(-P // 65536)
-    return max(lo, min(max(1, WGRAD_UNITS // (d.KH * d.KW * (d.Cout // 16))), max(1, P // 512)))
+    """Pixel splits of a conv's wgrad inside the batched launch (8-wave workgroups), by the library's own
+    rule (lbt_conv_wgrad_many_nsplit, conv_mfma.hip). Staged 3x3 body: each split = 8 waves x
+    `chunks_per_wave` 64-pixel chunks, a divisor of the chunk count. Other convs: ~16 workgroups
+    (split x tap x co slice) per conv."""
+    ns = _lib.load().lbt_conv_wgrad_many_nsplit(d, int(chunks_per_wave or WGRAD_CPW), WGRAD_UNITS)
+    if ns <= 0:
+        raise _lib.LbtError("lbt_conv_wgrad_many_nsplit = %d" % ns)
+    return ns
+
+
+def wgrad_many_blocks(d, nsplit):
+    """Workgroups lbt_conv_wgrad_many_i8 gives conv d's job at nsplit splits."""
+    nb = _lib.load().lbt_conv_wgrad_many_blocks(d, int(nsplit))
+    if nb <= 0:
+        raise _lib.LbtError("lbt_conv_wgrad_many_blocks = %d" % nb)
+    return nb
 
 
 def wgrad_nshard(d, nsplit):
