@@ -637,6 +637,31 @@ int lbt_bn_param_grads(const int64_t* sums, int32_t C, lbt_qdesc qrg, lbt_qdesc 
 /* ReLU_q forward (:986, tf.maximum(0,x)) and backward (TF _MaximumGrad: g where x > 0). */
 int lbt_relu_fwd(const float* x, float* y, int64_t n, void* stream);
 int lbt_relu_bwd(const float* g, const float* x, float* dx, int64_t n, void* stream);
+/* Dropout_q (:1025-1040: tf.cond(train, tf.nn.dropout(X, keep_prob), X); TF-1's dropout is
+ * div(x, keep_prob) * floor(keep_prob + uniform(x.shape))) on the build's noise stream. For the flat
+ * index i over the WHOLE tensor (batch included, no broadcast), n <= 2^34 elements (the 32-bit Philox
+ * block counter; more -> LBT_EINVAL), 0 < keep <= 1 (else LBT_EINVAL):
+ *   u_i = Philox4x32-10((i >> 2, did, step_lo, step_hi), (seed_lo, seed_hi))[i & 3] >> 8, times 2^-24
+ *   m_i = fl32(keep + u_i) >= 1 ? 1 : 0
+ *   y_i = fl32(x_i / keep) * m_i            (correctly rounded fp32 division, then an fp32 multiply)
+ * did is the layer's stream id (crc32 of its name, where a quantiser has its range variable's);
+ * step is the device step counter of the quantisers (step[0], read by the kernel).
+ * fwd: relu != 0 computes dropout(max(x, 0)) -- a ReLU_q (:983-990) folded in front.
+ * bwd: dx_i = fl32(g_i / keep) * m_i, the mask regenerated from its counter (none is stored), which is
+ * TF's gradient of the forward expression; relu_x != NULL (the folded ReLU's input) also zeroes dx where
+ * relu_x <= 0, as lbt_relu_bwd does. */
+int lbt_dropout_fwd(const float* x, float* y, int64_t n, float keep, const uint64_t* step, uint64_t seed,
+                    uint32_t did, int32_t relu, void* stream);
+int lbt_dropout_bwd(const float* g, float* dx, int64_t n, float keep, const uint64_t* step, uint64_t seed,
+                    uint32_t did, const float* relu_x, void* stream);
+/* Dropout_q (+ an optional folded ReLU_q) and the NEXT layer's input quantiser q (:287-288 Conv2d_q,
+ * :386 Dense_q) in one pass over x [rows, inner]: exactly the codes and the overflow counters (every
+ * shard) of lbt_dropout_fwd followed by lbt_dfxp_quantize(.., q, NULL, 0), without the fp32 dropout
+ * output. The dropout mask is indexed by the element's index in the whole tensor, the quantiser's
+ * noise by index mod inner; step and seed are q's. out_kind: LBT_OUT_I8 / _U8OFF / _I16
+ * (LBT_OUT_F32 -> LBT_EINVAL: float-mode layers run the separate launches). */
+int lbt_dropout_quantize(const float* x, void* out, int out_kind, int64_t rows, int64_t inner, float keep,
+                         uint32_t did, int32_t relu, lbt_qdesc q, void* stream);
 /* elementwise a + b (ResidualBlock_q :862 / :869). */
 int lbt_add(const float* a, const float* b, float* y, int64_t n, void* stream);
 /* AvgPool_q over the whole HxW map (:1017): y[n,c] = (sequential fp32 sum) * (1/(H*W)). */
@@ -951,7 +976,7 @@ typedef struct lbt_conv_fwd2 {
 } lbt_conv_fwd2;
 int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* p, void* stream);
 
-/* ABI version for the Python loader. */
+/* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

@@ -19,7 +19,7 @@ NSHARD = 32
 STEM_WG_PIXELS = 256  # LBT_STEM_WG_PIXELS
 CSTRIDE = 32  # int32 stride between overflow-counter shards (LBT_CSTRIDE)
 OUT_I8, OUT_U8OFF, OUT_I16, OUT_F32 = 0, 1, 2, 3
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_void_p, c_int32, c_int64, c_uint32, c_uint64, c_float = (
     ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float)
@@ -276,6 +276,9 @@ _SIGS = {
     "lbt_bn_param_grads": [_P, c_int32, QDesc, QDesc, _P, c_float, _P, _P, _P],
     "lbt_relu_fwd": [_P, _P, c_int64, _P],
     "lbt_relu_bwd": [_P, _P, _P, c_int64, _P],
+    "lbt_dropout_fwd": [_P, _P, c_int64, c_float, _P, c_uint64, c_uint32, c_int32, _P],
+    "lbt_dropout_bwd": [_P, _P, c_int64, c_float, _P, c_uint64, c_uint32, _P, _P],
+    "lbt_dropout_quantize": [_P, _P, c_int32, c_int64, c_int64, c_float, c_uint32, c_int32, QDesc, _P],
     "lbt_add": [_P, _P, _P, c_int64, _P],
     "lbt_maxpool_fwd": [_P, _P, _P, ConvDesc, _P],
     "lbt_maxpool_bwd": [_P, _P, _P, ConvDesc, _P],

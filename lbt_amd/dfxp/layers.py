@@ -78,6 +78,10 @@ DGRAD_BNA = os.environ.get("LBT_DGRAD_BNA_PY", "1") != "0"
 DGRAD_BN3 = os.environ.get("LBT_DGRAD_BN3_PY", "1") != "0"
 # ... and the forward chains read their BN's moments from one lbt_bn_moments launch (nrm.ms_in)
 CHAIN_MS = os.environ.get("LBT_CHAIN_MS", "1") != "0"
+# Dropout_q's wiring (feeds / relu): the mask drawn inside the next layer's input quantiser
+# (ops.dropout_quantize) and the ReLU in front folded into the dropout; LBT_DROPOUT_FUSE=0: every
+# layer runs its own launches (A/B, bit-identical)
+DROPOUT_FUSE = os.environ.get("LBT_DROPOUT_FUSE", "1") != "0"
 
 
 class _DgradIn:
@@ -193,9 +197,21 @@ def _conv_bwd_f32(layer, gq, d, dev):
     return dx
 
 
+def _x_codes(layer, X):
+    """X through the layer's input quantiser -- drawing the mask (and the folded ReLU) of the Dropout_q
+    in front on the way in when that layer handed its input through untouched (Dropout_q.fused)."""
+    out = layer._c.get("xq", X.shape, ops.out_dtype(layer.x_kind), X.device)
+    drop = layer.drop_in
+    if drop is not None and drop.fused:
+        return ops.dropout_quantize(X, drop.keep_prob, drop.did, layer.X_range, layer.x_kind, out=out,
+                                    relu=drop.folds_relu)
+    return ops.quantize(X, layer.X_range, layer.x_kind, out=out)
+
+
 class Layer_q:
     """Base class: identity forward, gradient pass-through backward (``:97-126``)."""
     _batched_q = False  # parameters quantised by the model's batched prologue (Model.forward)
+    drop_in = None  # the Dropout_q in front that feeds this layer (set by Dropout_q.feeds)
 
     def forward(self, X):
         self.X = X
@@ -373,8 +389,7 @@ class Conv2d_q(Layer_q):
         N, H, W, Cin = X.shape
         kh, kw, _, Cout = self.ksize
         self.d = d = ops.conv_desc(N, H, W, Cin, Cout, kh, kw, self.strides[1], self.strides[2], self.padding)
-        self.xq = ops.quantize(X, self.X_range, self.x_kind, out=self._c.get("xq", X.shape, ops.out_dtype(self.x_kind),
-                                                                                X.device))
+        self.xq = _x_codes(self, X)
         self.quantize_weights()
         y = self._c.get("y", (N, d.Ho, d.Wo, Cout), torch.float32, X.device)
         if self.x_mfma and self.w4:
@@ -555,8 +570,7 @@ class Dense_q(Layer_q):
                 ops.bias_add(y, _fq(self.b, self.b_range, self._c, "bq"), self.units)
             self.y = y
             return y
-        self.xq = ops.quantize(X, self.X_range, self.x_kind, out=self._c.get("xq", X.shape,
-                                                                              ops.out_dtype(self.x_kind), dev))
+        self.xq = _x_codes(self, X)
         if not (self._batched_q and self.ctx.params_ready):
             ops.quantize_weight(self.W, self.W_range, w_hwio=self.w_hwio)
         y = self._c.get("y", (N, self.units), torch.float32, dev)
@@ -930,6 +944,10 @@ class ReLU_q(Layer_q):
         if self.act_in_pool and X.shape[-1] % 4 == 0:
             self.y = X
             return X  # the pool computes pool(relu(X)) (ops.maxpool_relu_fwd)
+        self.in_drop = self.act_in_drop is not None and self.act_in_drop.folds_relu
+        if self.in_drop:
+            self.y = X
+            return X  # the dropout computes dropout(relu(X)), itself or inside the next quantiser
         self.y = self._c.get("y", X.shape, torch.float32, X.device)
         ops.relu_fwd(X, self.y)
         return self.y
@@ -938,9 +956,13 @@ class ReLU_q(Layer_q):
     mask_in_pool = False
     # set by the model builder when that pool also applies the activation (forward returns X)
     act_in_pool = False
+    # the Dropout_q behind this ReLU (a Flatten_q may sit between) that applies it, forward and
+    # backward, while it trains (set by Dropout_q.relu); in_drop: the last forward went that way
+    act_in_drop = None
+    in_drop = False
 
     def backward(self, grad, stochastic=True):
-        if self.mask_in_pool:
+        if self.mask_in_pool or self.in_drop:
             return grad
         dx = self._c.get("dx", grad.shape, torch.float32, grad.device)
         ops.relu_bwd(grad, self.X, dx)
@@ -1404,6 +1426,92 @@ class AvgPool_q(Layer_q):
 
     def info(self):
         return "avg pool: %dx%d stride %dx%d" % (self.ksize[1], self.ksize[2], self.strides[1], self.strides[2])
+
+
+class Dropout_q(Layer_q):
+    """``Dropout_q`` (``:1025-1040``): ``tf.nn.dropout(X, keep_prob)`` while training, the identity
+    otherwise. Per element i of the whole tensor, ``y = (X / keep) * (keep + u_i >= 1)`` with u_i from
+    the quantisers' Philox stream under this layer's id (``qid_of(name)``; the reference's layer has
+    no name: ``dropout%d`` in construction order within the context) -- DESIGN section 4. No mask is
+    kept: the backward regenerates it from the same counter, so both must run at the same step.
+
+    Wiring (what a model builder sets; ``LBT_DROPOUT_FUSE=0`` ignores it):
+    ``drop.feeds = next_layer`` (a Conv2d_q / Dense_q): forward returns X untouched and that layer
+    draws the mask inside its input quantiser (``ops.dropout_quantize``) -- the fp32 dropout output
+    is never written; ``drop.relu = relu_layer`` (the ReLU_q in front, a Flatten_q may sit between):
+    that ReLU returns its input and this layer computes ``dropout(max(X, 0))`` and both masks in its
+    backward. Neither applies while the layer is the identity (testing mode, ``keep_prob == 1``)."""
+
+    def __init__(self, keep_prob, training, name=None, ctx=None):
+        if not 0 < keep_prob <= 1:
+            raise ValueError("keep_prob must be in (0, 1], got %r" % (keep_prob,))
+        self.ctx = ctx = ctx or default_context()
+        self.keep_prob, self.train = keep_prob, bool(training)
+        self.name = name or "dropout%d" % (len(ctx.dropouts) + 1)
+        if self.name in ctx.dropouts:
+            raise ValueError("duplicate Dropout_q name %r (one mask stream per name)" % self.name)
+        ctx.dropouts[self.name] = self
+        self.did = qid_of(self.name)
+        self._feeds = self._relu = None
+        self._c = _Cache()
+
+    @property
+    def feeds(self):
+        return self._feeds
+
+    @feeds.setter
+    def feeds(self, layer):
+        if self._feeds is not None:
+            self._feeds.drop_in = None
+        self._feeds = layer
+        if layer is not None:
+            layer.drop_in = self
+
+    @property
+    def relu(self):
+        return self._relu
+
+    @relu.setter
+    def relu(self, layer):
+        if self._relu is not None:
+            self._relu.act_in_drop = None
+        self._relu = layer
+        if layer is not None:
+            layer.act_in_drop = self
+
+    @property
+    def active(self):
+        return self.train and self.keep_prob < 1
+
+    @property
+    def fused(self):
+        """The next layer's input quantiser applies this dropout (integer-code layers only)."""
+        return (DROPOUT_FUSE and self.active and self._feeds is not None
+                and not getattr(self._feeds, "fmode", False))
+
+    @property
+    def folds_relu(self):
+        return DROPOUT_FUSE and self.active and self._relu is not None
+
+    def forward(self, X):
+        self.X = X
+        self.relu_x = self._relu.X if self.folds_relu else None
+        if not self.active or self.fused:
+            self.y = X
+            return X
+        self.y = self._c.get("y", X.shape, torch.float32, X.device)
+        ops.dropout_fwd(X.contiguous(), self.y, self.keep_prob, self.ctx, self.did, relu=self.relu_x is not None)
+        return self.y
+
+    def backward(self, grad, stochastic=True):
+        if grad is None or not self.active:
+            return grad
+        dx = self._c.get("dx", grad.shape, torch.float32, grad.device)
+        ops.dropout_bwd(grad.contiguous(), dx, self.keep_prob, self.ctx, self.did, relu_x=self.relu_x)
+        return dx
+
+    def info(self):
+        return "dropout: %f" % self.keep_prob
 
 
 class Flatten_q(Layer_q):

@@ -511,6 +511,50 @@ def add(a, b, y):
     call("lbt_add", ptr(a), ptr(b), ptr(y), a.numel(), stream())
 
 
+# ----------------------------------------------------------------------------- dropout
+def dropout_fwd(x, y, keep, ctx, did, relu=False):
+    """Dropout_q forward (dynamic_fixed_point.py:1032-1036): y = (x / keep) * mask, the mask of stream
+    `did` at ctx's step and seed; relu: on max(x, 0) (a ReLU_q folded in front)."""
+    _check(x, torch.float32, "x")
+    _check(y, torch.float32, "y")
+    with _Timed("dropout_fwd_kernel", x.numel() * 8):
+        call("lbt_dropout_fwd", ptr(x), ptr(y), x.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
+             1 if relu else 0, stream())
+    return y
+
+
+def dropout_bwd(g, dx, keep, ctx, did, relu_x=None):
+    """dx = (g / keep) * mask (the forward's mask, regenerated); relu_x: the folded ReLU's input."""
+    _check(g, torch.float32, "g")
+    _check(dx, torch.float32, "dx")
+    if relu_x is not None:
+        _check(relu_x, torch.float32, "relu_x")
+        if relu_x.numel() != g.numel():
+            raise ValueError("relu_x has %d elements, the gradient %d" % (relu_x.numel(), g.numel()))
+    with _Timed("dropout_bwd_kernel", g.numel() * (8 if relu_x is None else 12)):
+        call("lbt_dropout_bwd", ptr(g), ptr(dx), g.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
+             ptr(relu_x), stream())
+    return dx
+
+
+def dropout_quantize(x, keep, did, q, kind, out=None, relu=False, desc=None):
+    """dropout_fwd + quantize(.., q, kind) in one pass (codes and counters identical), without the fp32
+    dropout output. desc: q's descriptor to use (e.g. ctx.noise_table_desc(q, inner))."""
+    _check(x, torch.float32, "x")
+    if kind == OUT_F32:
+        raise ValueError("dropout_quantize writes integer codes only (float-mode layers stay unfused)")
+    rows, inner = rows_inner(tuple(x.shape))
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype(kind), device=x.device)
+    q.observe(x.numel())
+    vec = inner % 4 == 0 and inner >= 64 and x.data_ptr() % 16 == 0
+    with _Timed("dropout_quantize_rows_kernel" if vec else "dropout_quantize_generic_kernel",
+                x.numel() * (4 + _code_bytes(kind))):
+        call("lbt_dropout_quantize", ptr(x), ptr(out), kind, rows, inner, float(keep), int(did), 1 if relu else 0,
+             q.desc if desc is None else desc, stream())
+    return out
+
+
 def avgpool_fwd(x, y, N, HW, C):
     call("lbt_avgpool_fwd", ptr(x), ptr(y), int(N), int(HW), int(C), stream())
 

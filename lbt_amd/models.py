@@ -3,7 +3,8 @@
 ``Model`` mirrors ``models.py:7-54``: it owns the layer list, runs the forward pass, the mean
 sparse softmax cross-entropy (``:30-32``) and the manual backward from d loss / d logits through
 ``reversed(layers)`` (``:47-51``). ``CIFAR10_Resnet`` / ``CIFAR10_Resnet20/32/44/56`` mirror
-``:371-470``. Inputs are NHWC fp32 CUDA tensors, labels int32.
+``:371-470``; ``PI_MNIST_Model`` / ``MNIST_Model`` / ``CIFAR10_Model`` / ``CIFAR10_VGG_Model`` mirror
+``:57-368``. Inputs are NHWC fp32 CUDA tensors (``[B, 784]`` for the PI model), labels int32.
 """
 import torch
 
@@ -30,6 +31,7 @@ class Model:
         self.layers = self.get_layers()
         if self.layers and hasattr(self.layers[0], "need_input_grad"):
             self.layers[0].need_input_grad = False  # d loss / d input is never consumed
+        self._wire_dropouts()
         self._c = _Cache()
         self.logits = None
         self.loss = None
@@ -114,21 +116,40 @@ class Model:
         self.logits = X
         return X
 
+    def _wire_dropouts(self):
+        """Every top-level Dropout_q's fusions (as pool_relu / act_in_pool are wired): its mask drawn
+        inside the input quantiser of the Conv2d_q / Dense_q behind it, and the ReLU_q in front (a
+        Flatten_q may sit between) folded into the dropout. LBT_DROPOUT_FUSE=0 leaves both unused."""
+        ls = self.layers
+        for i, l in enumerate(ls):
+            if not isinstance(l, L.Dropout_q):
+                continue
+            if i + 1 < len(ls) and isinstance(ls[i + 1], (L.Conv2d_q, L.Dense_q)):
+                l.feeds = ls[i + 1]
+            j = i - 2 if i >= 2 and isinstance(ls[i - 1], L.Flatten_q) else i - 1
+            if j >= 0 and isinstance(ls[j], L.ReLU_q):
+                l.relu = ls[j]
+
     def _norm_layers(self):
         return [l for l in self._walk() if isinstance(l, L.Normalization_q)]
 
+    def _mode_layers(self):
+        """The layers with a training / testing branch (``tf.cond(self.train, ..)``)."""
+        return [l for l in self._walk() if isinstance(l, (L.Normalization_q, L.Dropout_q))]
+
     def set_testing(self):
         """models.py:15 ``set_testing``: every Normalization_q normalises with its running averages
-        (dynamic_fixed_point.py:590-600). The layer-wise model only (a FusedResNet plan is built for
-        training-mode BatchNorm, which is also what the reference's test loop runs, trainer.py:164)."""
+        (dynamic_fixed_point.py:590-600) and every Dropout_q is the identity (:1032-1036). The layer-wise
+        model only (a FusedResNet plan is built for training-mode BatchNorm, which is also what the
+        reference's test loop runs, trainer.py:164)."""
         self.training = False
-        for n in self._norm_layers():
+        for n in self._mode_layers():
             n.train = False
 
     def set_training(self):
         """models.py:14 ``set_training``."""
         self.training = True
-        for n in self._norm_layers():
+        for n in self._mode_layers():
             n.train = True
 
     def compute_loss(self, labels):
@@ -272,3 +293,90 @@ class ImageNet_Resnet(Model):
 
 def ImageNet_Resnet50(bits, grad_bits=None, weight_decay=0, classes=1000, image=224, width=64, ctx=None):
     return ImageNet_Resnet(bits, (3, 4, 6, 3), grad_bits, width, classes, image, weight_decay, ctx=ctx)
+
+
+class _PlainModel(Model):
+    """The reference's four plain models (``models.py:57-368``): convolutions / dense layers with
+    biases, ReLU_q, MaxPool_q, Flatten_q and Dropout_q. A conv behind a ReLU_q (a pool or a dropout
+    between them keeps the sign) takes the unsigned-code path (``input_nonnegative``)."""
+
+    def _conv(self, name, ksize, padding, nonneg=True):
+        return L.Conv2d_q(name=name, bits=self.bits, ksize=ksize, strides=[1, 1, 1, 1], padding=padding,
+                          weight_decay=self.weight_decay, input_nonnegative=nonneg, ctx=self.ctx)
+
+    def _dense(self, name, in_units, units):
+        return L.Dense_q(name=name, bits=self.bits, in_units=in_units, units=units,
+                         weight_decay=self.weight_decay, ctx=self.ctx)
+
+    def _drop(self):
+        return L.Dropout_q(self.dropout, self.training, ctx=self.ctx)
+
+    @staticmethod
+    def _pool(k, padding):
+        return L.MaxPool_q(ksize=[1, k, k, 1], strides=[1, 2, 2, 1], padding=padding)
+
+
+class PI_MNIST_Model(_PlainModel):
+    """``models.py:57-88``: 784 - 1024 - 1024 - 10, dropout in front of dense2 and softmax."""
+
+    def __init__(self, bits, dropout=0.5, weight_decay=0, stochastic=False, ctx=None):
+        super().__init__(bits, [None, 784], dropout, weight_decay, stochastic, ctx)
+
+    def get_layers(self):
+        return [self._dense("dense1", 784, 1024), L.ReLU_q(), self._drop(),
+                self._dense("dense2", 1024, 1024), L.ReLU_q(), self._drop(),
+                self._dense("softmax", 1024, 10)]
+
+
+class MNIST_Model(_PlainModel):
+    """``models.py:91-152``: LeNet-5 on [28, 28, 1] (5x5 convs SAME / VALID / VALID, 2x2/2 VALID pools)."""
+
+    def __init__(self, bits, dropout=0.5, weight_decay=0, stochastic=False, ctx=None):
+        super().__init__(bits, [None, 28, 28, 1], dropout, weight_decay, stochastic, ctx)
+
+    def get_layers(self):
+        return [self._conv("conv1", [5, 5, 1, 6], "SAME", nonneg=False), L.ReLU_q(), self._pool(2, "VALID"),
+                self._conv("conv2", [5, 5, 6, 16], "VALID"), L.ReLU_q(), self._pool(2, "VALID"),
+                self._conv("conv3", [5, 5, 16, 120], "VALID"), L.ReLU_q(), L.Flatten_q(120), self._drop(),
+                self._dense("dense1", 120, 84), L.ReLU_q(), self._drop(),
+                self._dense("softmax", 84, 10)]
+
+
+class CIFAR10_Model(_PlainModel):
+    """``models.py:155-234``: three 5x5 SAME convs (64, 128, 128) each with a 3x3/2 SAME pool, dense
+    2048 - 400 - 10; dropout in front of conv2, conv3, dense1 and softmax."""
+
+    def __init__(self, bits, dropout=0.5, weight_decay=0, stochastic=False, ctx=None):
+        super().__init__(bits, [None, 32, 32, 3], dropout, weight_decay, stochastic, ctx)
+
+    def get_layers(self):
+        return [self._conv("conv1", [5, 5, 3, 64], "SAME", nonneg=False), L.ReLU_q(), self._pool(3, "SAME"),
+                self._drop(), self._conv("conv2", [5, 5, 64, 128], "SAME"), L.ReLU_q(), self._pool(3, "SAME"),
+                self._drop(), self._conv("conv3", [5, 5, 128, 128], "SAME"), L.ReLU_q(), self._pool(3, "SAME"),
+                L.Flatten_q(128 * 4 * 4),
+                self._drop(), self._dense("dense1", 128 * 4 * 4, 400), L.ReLU_q(),
+                self._drop(), self._dense("softmax", 400, 10)]
+
+
+class CIFAR10_VGG_Model(_PlainModel):
+    """``models.py:237-368``: conv pairs at width, 2 width, 4 width (the reference: 128, 256, 512) each
+    with a 3x3/2 SAME pool, dense 16 * 4 width - dense_units - dense_units - 10; dropout in front of
+    conv2-1, conv3-1 and the three dense layers. width / dense_units: a narrow instance for tests."""
+
+    def __init__(self, bits, dropout=0.5, weight_decay=0, stochastic=False, ctx=None, *, width=128,
+                 dense_units=1024):
+        self.width, self.dense_units = width, dense_units
+        super().__init__(bits, [None, 32, 32, 3], dropout, weight_decay, stochastic, ctx)
+
+    def get_layers(self):
+        w, u = self.width, self.dense_units
+        return [self._conv("conv1-1", [3, 3, 3, w], "SAME", nonneg=False), L.ReLU_q(),
+                self._conv("conv1-2", [3, 3, w, w], "SAME"), L.ReLU_q(), self._pool(3, "SAME"),
+                self._drop(), self._conv("conv2-1", [3, 3, w, 2 * w], "SAME"), L.ReLU_q(),
+                self._conv("conv2-2", [3, 3, 2 * w, 2 * w], "SAME"), L.ReLU_q(), self._pool(3, "SAME"),
+                self._drop(), self._conv("conv3-1", [3, 3, 2 * w, 4 * w], "SAME"), L.ReLU_q(),
+                self._conv("conv3-2", [3, 3, 4 * w, 4 * w], "SAME"), L.ReLU_q(), self._pool(3, "SAME"),
+                L.Flatten_q(4 * w * 4 * 4),
+                self._drop(), self._dense("dense1", 4 * w * 4 * 4, u), L.ReLU_q(),
+                self._drop(), self._dense("dense2", u, u), L.ReLU_q(),
+                self._drop(), self._dense("softmax", u, 10)]

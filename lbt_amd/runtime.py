@@ -82,6 +82,7 @@ class DfxpContext:
         self.nelem = torch.zeros(capacity, dtype=torch.float32, device=dev)
         self.quantizers = []
         self.by_name = {}
+        self.dropouts = {}  # Dropout_q name -> layer, in construction order (default names: dropout%d)
         # per-step integer reduction buffers (BN channel sums, grad column sums), bump-allocated
         # from one arena so a whole step zeroes them with ONE fill (see zero_sums).
         self.sums_arena = torch.zeros(sums_capacity, dtype=torch.int64, device=dev)

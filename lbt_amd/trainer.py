@@ -89,6 +89,11 @@ class Trainer:
             capture_comm = (dist_on and dist.get_backend(process_group) == "nccl"
                             and os.environ.get("LBT_CAPTURE_COMM", "1") == "1")
         self.capture_comm = bool(capture_comm) and dist_on
+        if self.dp and self._has_dropout(model):
+            # every rank would draw the same mask (the noise keys do not depend on the rank): the
+            # shards of one global batch need per-rank mask streams, which are not defined yet
+            raise NotImplementedError("data-parallel training of a model with Dropout_q layers is not "
+                                      "supported: per-rank dropout mask streams are not implemented")
         exact = self.dp and hasattr(model, "set_exchange")
         # layer-wise models (ResNet-50, configs[3]): the same exact int64 exchange when every gradient
         # is an integer numerator (integer-coded W / gamma / beta only; LBT_EXACT_LAYERWISE=0: fp32)
@@ -118,6 +123,12 @@ class Trainer:
         self._aug = None
         if logger is not None:
             logger.info("Model info:\n" + model.info())
+
+    @staticmethod
+    def _has_dropout(model):
+        from .dfxp.layers import Dropout_q
+        root = getattr(model, "model", model)
+        return hasattr(root, "_walk") and any(isinstance(l, Dropout_q) for l in root._walk())
 
     def _setup_exchange(self):
         """The exact exchange of a fused plan: buffer, descriptor, and the finish kernel's segments."""
@@ -434,9 +445,9 @@ class Trainer:
 
     def evaluate(self, X, y, batch_size=1000):
         """The reference's test loop (trainer.py:166-190): per batch of 1000 the forward pass in
-        training mode (batch-statistic BN, stochastic quantisers -- the reference never runs
-        set_testing, :164-165), loss and accuracy; returns (mean accuracy, mean loss) over the
-        batches. The overflow counters these forwards accumulate are discarded (the loop does not
+        training mode (batch-statistic BN, stochastic quantisers, and Dropout_q still dropping, at the
+        current step's mask -- the reference never runs set_testing, :164-165), loss and accuracy;
+        returns (mean accuracy, mean loss) over the batches. The overflow counters these forwards accumulate are discarded (the loop does not
         fetch update_range_op); BN running statistics are updated, as the reference's are."""
         dev = self.ctx.device
         saved = self.ctx.counts.clone()
