@@ -5,6 +5,9 @@
 // these fp32 kernels, exactly as TF computes them on the fake-quantised tensors (fp32 operands),
 // with every reduction accumulated in double in a fixed order (deterministic; within ~1 ulp of an
 // exact sum). Not the hot path: straightforward VALU loops.
+// Layers of 9..16 bits run here too (their codes do not fit the int8 weight / BN images): codes of at
+// most 17 bits make every product and sum exact in double, so the results are those of an exact
+// integer kernel, bit for bit.
 //
 //  lbt_conv_fwd_f32 / _dgrad_f32 / _wgrad_f32 (+ _wgrad_reduce_f32)   Conv2d_q :287-305, Dense_q :388-460
 //  lbt_chan_sums_f32                                                 per-channel sums (moments, dgamma)

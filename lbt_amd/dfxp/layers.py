@@ -10,10 +10,13 @@ Differences from TF (documented in DESIGN.md):
   (``layer.X_range`` etc. are :class:`~lbt_amd.runtime.Quantizer` objects); their updates are
   applied by ``ctx.update_range_op()`` -- the reference's ``'update_range'`` collection.
 * Quantised operands are kept as integer codes (int8 / offset-uint8 / int16) plus the shared
-  exponent; the convolutions and matmuls run as exact integer GEMMs.
+  exponent; the convolutions and matmuls run as exact integer GEMMs. That holds for ``bits <= 8``
+  (``weight_bits <= 8``, ``grad_bits <= 16``); wider layers contract the fake-quantised fp32 values
+  (float mode, ``float_mode`` below; DESIGN.md 2a has the width -> operand -> kernel table).
 * Outputs live in per-layer buffers that are reused every step (static-graph semantics).
-* ``Conv2d_q(..., input_nonnegative=True)`` declares a post-ReLU input: its (bits+1)-bit codes
-  are unsigned and take the int8 MFMA path; otherwise the signed codes take the VALU path.
+* ``Conv2d_q(..., input_nonnegative=True)`` declares a post-ReLU input: its 9-bit codes at
+  ``bits == 8`` are unsigned and take the int8 MFMA path, the signed ones the VALU path; below 8
+  bits the (bits+1)-bit codes are signed int8 either way and take the MFMA path.
 """
 import contextlib
 import os
@@ -143,12 +146,21 @@ def _as_param(t, ctx):
     return torch.as_tensor(t, dtype=torch.float32).to(ctx.device).contiguous()
 
 
-# ---- 17..32-bit quantisers (fp32.hip): weight_quantization's domain is 1 <= bits <= 32
-# (dynamic_fixed_point.py:21-23). Above 16 bits the integer codes no longer fit the int8 / int16 GEMM
-# operands; the quantiser then writes the fake-quantised fp32 values (the reference's own STE
-# output) and the layer contracts fp32 operands (fp32.hip), as TF does. bits == 32 is the bypass:
-# the tensor itself, no range update (:22-23).
-FLOAT_BITS = 16  # a layer whose quantisers exceed this many bits runs in float mode
+# ---- float mode (fp32.hip): weight_quantization's domain is 1 <= bits <= 32
+# (dynamic_fixed_point.py:21-23). The integer kernels hold weight, bias and BN codes in int8, X codes
+# in int8 / offset int8 / int16 (<= 9 bits) and gradient codes in int8 or int16. A layer one of whose
+# operands would not fit runs in float mode: its quantisers write the fake-quantised fp32 values (the
+# reference's own STE output) and the layer contracts fp32 operands (fp32.hip), as TF does. At 9..16
+# bits the codes and their sums are exact in the kernels' double accumulators, so float mode computes
+# what an integer kernel would, bit for bit. bits == 32 is the bypass: the tensor itself, no range
+# update (:22-23). DESIGN.md section 2a has the width -> operand -> kernel table.
+INT_BITS = 8     # widest `bits` / `weight_bits` of an integer-mode layer
+FLOAT_BITS = 16  # widest `grad_bits` of an integer-mode layer (int16 gradient codes)
+
+
+def float_mode(bits, grad_bits, weight_bits=None):
+    """True when a layer of these widths cannot run on the integer kernels."""
+    return bits > INT_BITS or (weight_bits or bits) > INT_BITS or (grad_bits or bits) > FLOAT_BITS
 
 
 def _check_bits(bits):
@@ -248,9 +260,9 @@ class Conv2d_q(Layer_q):
         self.target_overflow_rate, self.weight_decay = target_overflow_rate, weight_decay
         self.input_nonnegative = input_nonnegative
         self.need_input_grad = True  # the model clears it for its first layer (TF prunes that dX)
-        # float mode: a quantiser beyond 16 bits (X at bits + 1: bits >= 16; at bits == 32 the X
+        # float mode: an operand beyond the integer kernels' code types (at bits == 32 the X
         # quantiser is 33 bits and the reference's assertion fires in forward, :21,287-288)
-        self.fmode = max(bits + 1, grad_bits or bits, weight_bits or bits) > FLOAT_BITS
+        self.fmode = float_mode(bits, grad_bits, weight_bits)
         limit = (3 / (h * w * Cin)) ** 0.5
         self.W = _as_param(_rng(ctx, name + "/W").uniform(-limit, limit, size=ksize).astype(np.float32), ctx)
         self.dW = torch.zeros_like(self.W)
@@ -540,8 +552,8 @@ class Dense_q(Layer_q):
             self.b = torch.zeros(units, dtype=torch.float32, device=ctx.device)
             self.db = torch.zeros_like(self.b)
             self.b_range = ctx.quantizer(name + "/b_range", bits, bias_range, t)
-        self.fmode = max(bits, grad_bits, weight_bits) > FLOAT_BITS
-        self.x_kind = OUT_F32 if self.fmode else (OUT_I8 if bits <= 8 else OUT_I16)
+        self.fmode = float_mode(bits, grad_bits, weight_bits)
+        self.x_kind = OUT_F32 if self.fmode else OUT_I8
         self.w_hwio = torch.zeros((in_units, units), dtype=torch.int8, device=ctx.device)
         # wide heads (ResNet-50's fc): int8-MFMA GEMMs on packed images of the quantised W
         self.mfma = ops.dense_mfma_ok(in_units, units, bits, weight_bits) and not self.fmode
@@ -735,7 +747,7 @@ class Normalization_q(Layer_q):
         self.X_mean_running = torch.zeros(num_features, dtype=torch.float32, device=ctx.device)
         self.X_var_running = torch.ones(num_features, dtype=torch.float32, device=ctx.device)
         self.ms = torch.zeros(2 * num_features, dtype=torch.float32, device=ctx.device)
-        self.fmode = max(bits, grad_bits) > FLOAT_BITS
+        self.fmode = float_mode(bits, grad_bits)
         self._c = _Cache()
 
     def norm_desc(self, q, chsum, n):
@@ -837,7 +849,7 @@ class Rescale_q(Layer_q):
         self.grad_bits = grad_bits = grad_bits or bits
         self.grad_range = ctx.quantizer(name + "/grad_range", grad_bits, grad_range, t)
         self.gb = torch.zeros(2 * num_features, dtype=torch.float32, device=dev)
-        self.fmode = max(bits, grad_bits) > FLOAT_BITS
+        self.fmode = float_mode(bits, grad_bits)
         self._c = _Cache()
 
     def param_slots(self):

@@ -57,6 +57,39 @@ class _Block:
         self.blk = blk
 
 
+def _check_plan_model(model):
+    """Refuse, before anything is allocated or launched, a model the plan was not written for. The
+    plan hard-codes: conv1 -> BatchNorm_q -> ReLU_q -> ResidualBlock_q ... -> pool -> flatten ->
+    Dense_q, no biases; every operand an integer code -- int16 image codes for conv1, offset-int8
+    codes of the post-ReLU block inputs (a quantiser of at most 9 bits), int8 weight, BN, dense and
+    gradient codes. That is bits <= 8 with weight_bits <= 8 and grad_bits <= 8; any wider layer runs
+    in float mode (or on int16 gradient codes), which no launch of the plan reads."""
+    from .dfxp import layers as Lq
+    ls = model.layers
+    ok = (len(ls) >= 7 and isinstance(ls[0], Lq.Conv2d_q) and isinstance(ls[1], Lq.BatchNorm_q)
+          and isinstance(ls[2], Lq.ReLU_q) and all(type(b) is Lq.ResidualBlock_q for b in ls[3:-3])
+          and isinstance(ls[-3], Lq.AvgPool_q) and isinstance(ls[-2], Lq.Flatten_q)
+          and isinstance(ls[-1], Lq.Dense_q))
+    if not ok:
+        raise NotImplementedError("FusedResNet runs the CIFAR ResNet layout (conv1, BatchNorm_q, ReLU_q, "
+                                  "ResidualBlock_q blocks, AvgPool_q, Flatten_q, Dense_q) only; got %s"
+                                  % type(model).__name__)
+    for l in model._walk():
+        if not isinstance(l, (Lq.Conv2d_q, Lq.Dense_q, Lq.Normalization_q, Lq.Rescale_q)):
+            continue
+        bits, wb, gb = l.bits, getattr(l, "weight_bits", l.bits), l.grad_bits
+        if l.fmode or bits > 8 or wb > 8 or gb > 8:
+            raise NotImplementedError(
+                "FusedResNet runs integer codes of at most 8 bits (9-bit unsigned conv inputs); layer %s has "
+                "bits=%d, weight_bits=%d, grad_bits=%d: train this width with the layer-wise model"
+                % (l.name, bits, wb, gb))
+        if getattr(l, "use_bias", False):
+            raise NotImplementedError("FusedResNet has no bias launches; layer %s has use_bias=True" % l.name)
+    for b in ls[3:-3]:
+        if not isinstance(b.residual.layers[1], Lq.BatchNorm_q):
+            raise NotImplementedError("FusedResNet needs batch_norm=True blocks; %s has none" % b.name)
+
+
 class FusedResNet:
     """Drop-in for the Trainer (forward / compute_loss / backward / param_slots / ctx / loss)."""
 
@@ -69,6 +102,7 @@ class FusedResNet:
         its HIP graph (RCCL) or runs the step eagerly (gloo).
         force_sync_bn: keep the collectives at world size 1 (tests of the captured path: a sum over
         one rank is the identity, so the step must equal the plain plan bit for bit)."""
+        _check_plan_model(model)
         self.model = model
         self.ctx = model.ctx
         self.sync_bn = bool(sync_bn) and (self.ctx.world_size > 1 or bool(force_sync_bn))

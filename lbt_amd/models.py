@@ -64,7 +64,7 @@ class Model:
         wjobs, starts, qjobs = [], [0], []
         for layer in self._walk():
             if getattr(layer, "fmode", False):
-                continue  # 17..32-bit layers quantise their own parameters as fp32 values
+                continue  # float-mode layers quantise their own parameters as fp32 values
             if isinstance(layer, L.Conv2d_q) and not layer.mfma and not getattr(layer, "w4", False) \
                     and layer.ksize[3] % 4 == 0:
                 kh, kw, ci, co = layer.ksize

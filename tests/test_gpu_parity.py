@@ -42,6 +42,18 @@ def decode(t, kind):
     ((128, 10), 8, -5, True, OUT_I8, -0.01, 0.01),
     ((4, 6, 6, 8), 4, 1, True, OUT_I8, -2.0, 2.0),
     ((4, 6, 6, 8), 12, 2, True, OUT_I16, -5.0, 5.0),
+] + [
+    # every other width of the integer operands and of the 9..16-bit float path, and the two ends of
+    # the exponent domain (e = bits - I - 1 = 0 and 30), a 4-D and a ragged shape, both roundings;
+    # inputs uniform in +-1.5 * 2**I, so both overflow counters count
+    (shape, bits, I, stoch, kind, -1.5 * 2.0 ** I, 1.5 * 2.0 ** I)
+    for bits, I, kind in [(1, 0, OUT_I8), (2, -1, OUT_I8), (3, 1, OUT_I8), (5, 2, OUT_I8), (7, -3, OUT_I8),
+                          (10, 2, OUT_I16), (13, 0, OUT_I16), (16, 2, OUT_I16),
+                          (3, 0, OUT_F32), (9, 2, OUT_F32), (12, -2, OUT_F32), (16, 1, OUT_F32),
+                          (8, 7, OUT_I8), (16, 15, OUT_I16), (16, 15, OUT_F32),       # e = 0
+                          (7, -24, OUT_I8), (16, -15, OUT_I16), (16, -15, OUT_F32)]   # e = 30
+    for shape in [(4, 6, 6, 8), (3, 7, 5)]
+    for stoch in (True, False)
 ])
 def test_quantize_codes_and_counts(shape, bits, I, stoch, kind, lo, hi):
     rng = np.random.default_rng(abs(hash((shape, bits, I))) % 2**32)
@@ -58,6 +70,9 @@ def test_quantize_codes_and_counts(shape, bits, I, stoch, kind, lo, hi):
         assert np.array_equal(got, ref)
     c = ctx.counts_view()[0].sum(0).cpu().tolist()
     assert tuple(c) == odfxp.overflow_counts(x, bits, I)
+    if hi == 1.5 * 2.0 ** I and lo == -hi:
+        assert 0 < c[0] < c[1] < x.size, "both overflow counters must count in these cases"
+        assert len(np.unique(ref)) >= min(3, 2 ** bits)
 
 
 def test_quantize_channel_sums_and_range_update():
@@ -547,6 +562,34 @@ def test_torch_face_conv_matches_layer():
     dxr = ref.backward(g.transpose(0, 2, 3, 1).copy(), octx)
     assert np.array_equal(xt.grad.permute(0, 2, 3, 1).cpu().numpy(), dxr)
     assert np.array_equal(m.weight.grad.permute(2, 3, 1, 0).cpu().numpy(), ref.dW)
+    # away from 8 bits: 6 (signed int8 X codes on the register MFMA kernels) and 12 (float mode); the
+    # weight and gradient ranges follow the data, so that the narrow codes are not all zero
+    for bits in (6, 12):
+        ctx = DfxpContext(seed=8 + bits)
+        name = "tc%d" % bits
+        m = Conv2d_q(bits, 16, 16, kernel_size=3, stride=1, padding=1, bias=False, ctx=ctx, name=name,
+                     input_nonnegative=True)
+        assert (m.layer.fmode, m.layer.mfma, m.layer.x_kind) == ((True, False, OUT_F32) if bits > 8 else
+                                                                 (False, True, OUT_I8))
+        ranges = {name + "/W_range": -2, name + "/X_range": 1, name + "/grad_range": -3}
+        ctx.set_ranges(ranges)
+        ref = onn.Conv2dQ(name, bits, [3, 3, 16, 16], [1, 1, 1, 1], "SAME", 0.0)
+        ref.W = m.weight.detach().permute(2, 3, 1, 0).cpu().numpy().copy()
+        xt = torch.from_numpy(x).to(DEV).requires_grad_(True)
+        y = m(xt)
+        octx = onn.Ctx(dict(ranges), 0, 8 + bits)
+        yr = ref.forward(x.transpose(0, 2, 3, 1).copy(), octx)
+        assert np.array_equal(y.detach().permute(0, 2, 3, 1).cpu().numpy(), yr)
+        g = rng.uniform(-0.15, 0.15, size=y.shape).astype(np.float32)
+        y.backward(torch.from_numpy(g).to(DEV))
+        dxr = ref.backward(g.transpose(0, 2, 3, 1).copy(), octx)
+        for r in ("/X_range", "/W_range", "/grad_range"):
+            rec = octx.record[name + r]
+            assert np.count_nonzero(rec) >= rec.size // 4 and len(np.unique(rec)) >= 3, r
+        assert np.array_equal(xt.grad.permute(0, 2, 3, 1).cpu().numpy(), dxr)
+        assert np.array_equal(m.weight.grad.permute(2, 3, 1, 0).cpu().numpy(), ref.dW)
+        ctx.update_range_op()
+        assert ctx.ranges() == octx.new_ranges()
 
 
 @pytest.mark.parametrize("shape", ["chain", "parallel"])
