@@ -361,7 +361,9 @@ int lbt_conv_stem_wide_wgrad(const int16_t* x, int32_t x_bits, const void* g, in
  * if run_mean != NULL, the running averages avg = momentum*avg + one_minus_momentum*x
  * (:601-612).
  * frozen != 0: the testing branch of the tf.cond (:590-600, set_testing, models.py:15): mu and
- * var are the running averages (chsum unused), sigma = sqrtf(run_var + eps), nothing updated.
+ * var are the running averages (chsum unused), sigma = sqrtf(run_var + eps), nothing updated
+ * (lbt_bn_chain_fwd still writes ms when ms != NULL; lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8
+ * take a frozen chain as a forward-only launch, see there).
  * ms_in != 0 (lbt_bn_chain_fwd only): ms already holds this step's [mu | sigma] (lbt_bn_moments ran
  * on this descriptor): the chain reads its channels' two floats instead of reducing the sums in
  * every workgroup, and updates nothing. Either every normalising branch of a chain sets ms_in or
@@ -581,7 +583,17 @@ int lbt_conv_bwd2_fused_i8(const lbt_conv_bwd2* p, void* stream);
  * update (workgroup 0) come from the owning workgroup only: every output is bit-identical to
  * lbt_bn_chain_fwd followed by lbt_conv_fwd_i8. Shapes as lbt_conv_bwd_fused_i8; chains: int8
  * Normalization_q inputs, Rescale_q codes stored, ReLU, stochastic noise tables, 1 or 2 branches,
- * optional residual and y; w4: wf is the packed 4-bit image. Else LBT_EINVAL.                    */
+ * optional residual and y; w4: wf is the packed 4-bit image. Else LBT_EINVAL.
+ * Testing mode (Model.set_testing, models.py:15): when EVERY normalising branch of c has
+ * nrm.frozen != 0 the launch is forward-only -- mu = run_mean, sigma = sqrtf(run_var + eps) exactly as
+ * lbt_bn_norm's frozen branch (nrm.chsum unused, may be NULL; ms and the running averages are not
+ * written), no overflow counting and no channel sums. It requires counts == NULL ("no stats") in
+ * c.b*.qr, c.qo1 and qout, and ychsum == NULL (the next BN is frozen too and reads no sums). The
+ * stores that only the backward reads become optional: c.b*.rout (R codes) and c.o1 (X codes: they
+ * then live in LDS only) may be NULL; c.o1_kind is read only with c.o1; y stays where the chain has
+ * it. yq and y are bit-identical to lbt_bn_chain_fwd (frozen) followed by lbt_conv_fwd_i8, and so are
+ * rout / o1 where given. One branch frozen and the other not: LBT_EINVAL (half a moments update).
+ * Without a frozen branch every check above holds unchanged (chsum, o1, rout required).           */
 typedef struct lbt_conv_fwd {
   lbt_chain_fwd c;
   const int8_t* wf; int32_t ksf; int32_t w4; const int32_t* wcolsum; lbt_conv_desc d; lbt_qdesc qw;
@@ -964,7 +976,11 @@ int lbt_softmax_xent_wide_n(const float* z, const int32_t* labels, int32_t N, in
  * into LDS, both convs from there (as lbt_conv_fwd_pair_i8: wf1 / wfs, their wcolsum offset
  * corrections), and each conv's quantising epilogue (yq1 / qout1 / ychsum1, yqs / qouts / ychsums).
  * Bit-identical to lbt_bn_chain_fwd followed by lbt_conv_fwd_pair_i8. Shapes: d1 3x3 stride 2 SAME
- * (pads 0 / 1), ds 1x1 stride 2, Cin = C in {16, 32}, Cout = 2C, W * C = 512, Ho % 4 == 0. */
+ * (pads 0 / 1), ds 1x1 stride 2, Cin = C in {16, 32}, Cout = 2C, W * C = 512, Ho % 4 == 0.
+ * Testing mode: c.b1.nrm.frozen != 0 selects the forward-only launch, as lbt_conv_fwd_fused_i8's:
+ * running averages, counts == NULL in c.b1.qr, c.qo1, c.qo2, qout1 and qouts, ychsum1 == ychsums ==
+ * NULL; c.b1.rout, c.o1 and c.o2 may be NULL (y and the residual stay required). yq1, yqs and y are
+ * bit-identical to lbt_bn_chain_fwd (frozen) followed by lbt_conv_fwd_pair_i8.                   */
 typedef struct lbt_conv_fwd2 {
   lbt_chain_fwd c;
   const int8_t* wf1; int32_t ksf1; const int32_t* wcolsum1;
@@ -976,7 +992,9 @@ typedef struct lbt_conv_fwd2 {
 } lbt_conv_fwd2;
 int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* p, void* stream);
 
-/* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). */
+/* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
+ * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
+ * frozen chain used to return LBT_EINVAL.                                                        */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

@@ -93,8 +93,13 @@ def _check_plan_model(model):
 class FusedResNet:
     """Drop-in for the Trainer (forward / compute_loss / backward / param_slots / ctx / loss)."""
 
-    def __init__(self, model, sync_bn=False, process_group=None, force_sync_bn=False):
-        """sync_bn: data-parallel parity mode -- every BatchNorm takes its moments (forward) and its
+    def __init__(self, model, sync_bn=False, process_group=None, force_sync_bn=False, inference=False):
+        """inference: a forward-only plan in testing mode (Model.set_testing, models.py:15): every
+        Normalization_q normalises with its running averages on the frozen fused kernels
+        (fused_infer.py). forward / compute_loss only; it changes neither the context (exponents,
+        counters, step, element counts) nor the running statistics, so it may run between two replays
+        of a captured training step. sync_bn is ignored (no batch statistics).
+        sync_bn: data-parallel parity mode -- every BatchNorm takes its moments (forward) and its
         pass-A sums (backward) over the GLOBAL batch: the per-rank integer sums are all-reduced
         (exact) before the kernel that consumes them, so N ranks of b samples compute what one
         process computes on the N*b batch (tf.nn.moments over the whole batch,
@@ -105,7 +110,8 @@ class FusedResNet:
         _check_plan_model(model)
         self.model = model
         self.ctx = model.ctx
-        self.sync_bn = bool(sync_bn) and (self.ctx.world_size > 1 or bool(force_sync_bn))
+        self.inference = bool(inference)
+        self.sync_bn = (bool(sync_bn) and (self.ctx.world_size > 1 or bool(force_sync_bn))) and not self.inference
         self.pg = process_group
         self.xchg = None  # data-parallel exchange descriptor (Trainer.set_exchange)
         L = model.layers
@@ -221,7 +227,12 @@ class FusedResNet:
             f()
         return self.loss
 
+    def _training_only(self, what):
+        if self.inference:
+            raise RuntimeError("FusedResNet(inference=True) is a forward-only inference plan: no %s" % what)
+
     def backward(self):
+        self._training_only("backward()")
         if self.xchg is not None:
             raise NotImplementedError("the data-parallel exchange runs with the fused head (train_fwd_bwd)")
         for f in self._hbwd + self._bwd + self._tail_sep:
@@ -230,6 +241,7 @@ class FusedResNet:
     def set_exchange(self, xchg):
         """Write the step's gradient numerators / counters / loss into the exchange buffer instead of
         dequantising them (lbt_step_reduce_x); set before the first step."""
+        self._training_only("set_exchange()")
         if self._shape is not None:
             raise RuntimeError("set_exchange after the plan was built")
         self.xchg = xchg
@@ -247,6 +259,7 @@ class FusedResNet:
     def set_optimizer(self, flat, lr, momentum):
         """MomentumOptimizer's flat buffers and hyper-parameters (trainer.py:79-84) for the fused update
         (train_fwd_bwd(update=True)); call again when lr changes, before the step is re-captured."""
+        self._training_only("set_optimizer()")
         ctx = self.ctx
         u = self._upd
         u.w, u.a, u.g = flat.w.data_ptr(), flat.a.data_ptr(), flat.g.data_ptr()
@@ -272,6 +285,7 @@ class FusedResNet:
         (lbt_head_fwd_bwd): same results bit for bit as the three calls. update=True (and
         updates_in_step()): the last launch also applies SGD-momentum and update_range (the Trainer's
         optimiser step, bit-identical). Returns whether it did."""
+        self._training_only("train_fwd_bwd()")
         self._ensure(X)
         self._bind(X, labels)
         tail = self.step_tail(update)
@@ -321,19 +335,9 @@ class FusedResNet:
         self._shape = tuple(X.shape)
         self._build(X)
 
-    def _build(self, X):
-        if not getattr(self.model, "training", True):
-            raise NotImplementedError("FusedResNet runs training-mode BatchNorm; use the layer-wise model after "
-                                      "set_testing()")
-        ctx = self.ctx
+    @staticmethod
+    def _launcher(lib):
         st = _lib.stream
-        N, H, W, Cin0 = X.shape
-        self._X = self._X_own = self.input_buffer(X.shape)
-        self._labels = self._labels_own = self.label_buffer(N)
-        fwd, bwd = [], []
-        lib = _lib.load()
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=ctx.device)
 
         def L(name, *args, k=None, nb=0):
             """A prebuilt launch; `k` / `nb` = kernel name and algorithmic bytes for the roofline hook."""
@@ -348,6 +352,24 @@ class FusedResNet:
             run.kname = kname
             run.nbytes = nb
             return run
+        return L
+
+    def _build(self, X):
+        if self.inference:
+            from . import fused_infer
+            return fused_infer.build(self, X)
+        if not getattr(self.model, "training", True):
+            raise NotImplementedError("FusedResNet runs training-mode BatchNorm; build the testing-mode plan with "
+                                      "FusedResNet(model, inference=True)")
+        ctx = self.ctx
+        N, H, W, Cin0 = X.shape
+        self._X = self._X_own = self.input_buffer(X.shape)
+        self._labels = self._labels_own = self.label_buffer(N)
+        fwd, bwd = [], []
+        lib = _lib.load()
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=ctx.device)
+        L = self._launcher(lib)
 
         self._nd, njobs = {}, []
         self._exps_snap = self._buf("exps_snap", tuple(ctx.exps.shape), torch.int32)

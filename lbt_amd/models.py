@@ -139,9 +139,12 @@ class Model:
 
     def set_testing(self):
         """models.py:15 ``set_testing``: every Normalization_q normalises with its running averages
-        (dynamic_fixed_point.py:590-600) and every Dropout_q is the identity (:1032-1036). The layer-wise
-        model only (a FusedResNet plan is built for training-mode BatchNorm, which is also what the
-        reference's test loop runs, trainer.py:164)."""
+        (dynamic_fixed_point.py:590-600) and every Dropout_q is the identity (:1032-1036). This switches
+        the layer-wise model. On the fused kernels the same mode is a plan of its own,
+        FusedResNet(model, inference=True) (forward-only, bit-identical to this model's forward in
+        testing mode; it does not need set_testing()); a training FusedResNet refuses a testing-mode
+        model. The reference's test loop stays in training mode (trainer.py:164):
+        Trainer.evaluate(testing=True) is the testing-mode loop."""
         self.training = False
         for n in self._mode_layers():
             n.train = False

@@ -443,12 +443,60 @@ class Trainer:
             return self._eval[n], False
         return m, True
 
-    def evaluate(self, X, y, batch_size=1000):
+    def _evaluate_testing(self, X, y, batch_size):
+        """evaluate(testing=True): the test loop in testing mode (Model.set_testing, models.py:15) -- every
+        BatchNorm normalises with its running averages and nothing moves. A FusedResNet runs one
+        forward-only inference plan per test-batch size (keys ("testing", n) of self._eval), which
+        touches neither the counters nor the element counts; a layer-wise model is wrapped in
+        set_testing() / set_training() and its counters and element counts are restored."""
+        from .fused import FusedResNet
+        dev = self.ctx.device
+        m = self.model
+        fused = isinstance(m, FusedResNet)
+        if not fused:
+            was_training = getattr(m, "training", True)
+            saved, saved_nelem = self.ctx.counts.clone(), self.ctx.nelem.clone()
+            m.set_testing()
+        acc_sum, loss_sum, nb = 0.0, 0.0, 0
+        try:
+            for b in range(0, len(X), batch_size):
+                Xb = torch.as_tensor(X[b:b + batch_size], dtype=torch.float32).to(dev).contiguous()
+                yb = torch.as_tensor(y[b:b + batch_size], dtype=torch.int32).to(dev)
+                p = m
+                if fused:
+                    key = ("testing", len(Xb))
+                    if key not in self._eval:
+                        self._eval[key] = FusedResNet(m.model, inference=True)
+                    p = self._eval[key]
+                logits = p.forward(Xb)
+                loss = p.compute_loss(yb)
+                acc = (logits.argmax(dim=1).to(torch.int32) == yb).float().mean()
+                acc_sum += float(acc.item())
+                loss_sum += float(loss.item())
+                nb += 1
+        finally:
+            if not fused:
+                if was_training:
+                    m.set_training()
+                self.ctx.counts.copy_(saved)
+                self.ctx.nelem.copy_(saved_nelem)
+                for q in self.ctx.quantizers:  # (as evaluate: the cached counts describe the test batches)
+                    q._nelem = None
+                self._graphs = None
+        return acc_sum / max(nb, 1), loss_sum / max(nb, 1)
+
+    def evaluate(self, X, y, batch_size=1000, testing=False):
         """The reference's test loop (trainer.py:166-190): per batch of 1000 the forward pass in
         training mode (batch-statistic BN, stochastic quantisers, and Dropout_q still dropping, at the
         current step's mask -- the reference never runs set_testing, :164-165), loss and accuracy;
         returns (mean accuracy, mean loss) over the batches. The overflow counters these forwards accumulate are discarded (the loop does not
-        fetch update_range_op); BN running statistics are updated, as the reference's are."""
+        fetch update_range_op); BN running statistics are updated, as the reference's are.
+        testing=True: the same loop and return value in testing mode instead (running-average BN, Dropout_q
+        the identity; what a trained network is deployed as): nothing is updated. A FusedResNet runs it on
+        forward-only inference plans (FusedResNet(model, inference=True)), a layer-wise model between
+        set_testing() and set_training()."""
+        if testing:
+            return self._evaluate_testing(X, y, batch_size)
         dev = self.ctx.device
         saved = self.ctx.counts.clone()
         saved_nelem = self.ctx.nelem.clone()  # an eval plan's build declares its own element counts
