@@ -13,6 +13,7 @@
 
 #include "bn_moments.h"
 #include "chain_flags.h"
+#include "env.h"
 #include "pk2.h"
 
 using namespace lbt;
@@ -657,17 +658,11 @@ __global__ void param_grads_kernel(const int64_t* sums, int C, lbt_qdesc qrg, lb
 bool grid_for(int64_t rows, int64_t inner, dim3& grid, int& rpt, int64_t dflt = 512) {
   const int64_t groups = inner / 4;
   const int64_t gblocks = (groups + kThreads - 1) / kThreads;
-  static const int64_t env_target = [] {
-    const char* e = getenv("LBT_CHAIN_BLOCKS");
-    return (int64_t)(e ? atoi(e) : 0);
-  }();
+  static const int64_t env_target = getenv_int("LBT_CHAIN_BLOCKS", 0);
   const int64_t target = env_target > 0 ? env_target : dflt;
   // a workgroup's fixed costs (moment prologue, counter / channel-sum flush) must amortise over
   // enough rows: at least min_rpt per thread even if that leaves fewer than `target` workgroups
-  static const int64_t min_rpt = [] {
-    const char* e = getenv("LBT_CHAIN_MINRPT");
-    return (int64_t)(e ? atoi(e) : 1);
-  }();
+  static const int64_t min_rpt = getenv_int("LBT_CHAIN_MINRPT", 1);
   int64_t r = (gblocks * rows) / target;
   if (r < min_rpt) r = min_rpt;
   if (r > rows) r = rows;

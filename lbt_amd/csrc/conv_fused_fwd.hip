@@ -1,6 +1,7 @@
 // conv_fused_fwd.hip -- the fused conv forward entry points and the training-mode instantiations of
 // conv_fused_fwd.h's kernels (the testing-mode ones: conv_fused_infer.hip).
 #include "conv_fused_fwd.h"
+#include "env.h"
 
 using namespace lbt;
 
@@ -21,17 +22,11 @@ extern "C" int lbt_conv_fused_tile_rows(int32_t Cin, int64_t N, int32_t H) {
   if (Cin != 16 && Cin != 32 && Cin != 64) return -LBT_EINVAL;
   const int CS = Cin / 16;
   if (CS != 1) {
-    static const int force23 = [] {
-      const char* e = getenv("LBT_TILE_ROWS23");
-      return e ? atoi(e) : 0;
-    }();
+    static const int force23 = getenv_int("LBT_TILE_ROWS23", 0);
     if (force23 == 4 || H % 4) return 4;
     return (force23 == 2 || N * H / 4 < 256) ? 2 : 4;
   }
-  static const int force = [] {
-    const char* e = getenv("LBT_TILE_ROWS1");
-    return e ? atoi(e) : 0;
-  }();
+  static const int force = getenv_int("LBT_TILE_ROWS1", 0);
   if (force == 2 || force == 4 || force == 8) return H % force ? 8 : force;  // (16-row tiles at B=128: 0.447 vs 0.429 ms)
   if (N * H / 8 >= 256 || H % 4) return 8;
   return (N * H / 4 < 256 && H % 2 == 0) ? 2 : 4;  // (2-row tiles: B = 16, as the wide stages below)

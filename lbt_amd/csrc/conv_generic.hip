@@ -6,7 +6,7 @@
 //   * channel counts that are not multiples of 16 (conv1 Cin=3, Dense_q 64->10 run as a
 //     1x1 conv on [B,1,1,C], custom.py's MNIST convs).
 // Exact integer arithmetic, so results are bit-identical to the MFMA path and the oracle.
-#include "dfxp_device.h"
+#include "conv_epilogue.h"
 
 using namespace lbt;
 
@@ -147,11 +147,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_generic_kernel(const TX* __res
     const int o = o0 + threadIdx.x + j * blockDim.x;
     if (o < o1) dst[o] = acc[j];
   }
-}
-
-bool desc_ok(const lbt_conv_desc& d) {
-  return d.N > 0 && d.H > 0 && d.W > 0 && d.KH > 0 && d.KW > 0 && d.SH > 0 && d.SW > 0 && d.Ho > 0 &&
-         d.Wo > 0 && d.Cin > 0 && d.Cout > 0;
 }
 
 }  // namespace

@@ -68,7 +68,7 @@ namespace lbt {
 // reader 4.36 -> 4.09 / 6.38 -> 6.16 us with 16-B stores, 6.07 -> 5.27 us with 4-B stores). Seven in
 // eight readers sit on another XCD, whose L2 never held the line. NOT for the streaming wide-layer
 // kernels (ResNet-50: tens to hundreds of MB per launch): there the same stores cost 42.2 -> 47.9 ms
-// per step (bn.hip, bn_wide.hip, igemm.hip, quantize.hip keep plain stores). 4- and 8-byte: a relaxed agent-
+// per step (bn.hip, bn_wide.hip, igemm*.hip, quantize.hip keep plain stores). 4- and 8-byte: a relaxed agent-
 // scope atomic store (the compiler's own sc1 store); 16-byte: a raw buffer store with the sc1 bit.
 // -DLBT_PLAIN_OUT (scratch A/B builds): plain stores.
 #ifdef LBT_PLAIN_OUT

@@ -13,7 +13,7 @@
 //  lbt_chan_sums_f32                                                 per-channel sums (moments, dgamma)
 //  lbt_bn_f32_fwd / lbt_bn_f32_bwd                                   Normalization_q :584-623
 //  lbt_affine_f32 / lbt_affine_grads_f32                             Rescale_q :677-691
-#include "dfxp_device.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -241,10 +241,7 @@ __global__ void affine_grads_f32_kernel(const double* __restrict__ part, int nsp
   dbeta[c] = (float)sg;
 }
 
-bool desc_ok(const lbt_conv_desc& d) {
-  return d.N > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.KH > 0 && d.KW > 0 && d.SH > 0 && d.SW > 0 &&
-         d.Ho > 0 && d.Wo > 0;
-}
+using lbt::desc_ok;
 
 unsigned nblk(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
 

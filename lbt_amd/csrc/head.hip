@@ -16,6 +16,7 @@
 // Reference: AvgPool_q dynamic_fixed_point.py:1009-1022, Dense_q :319-395 / :441-466,
 // loss models.py:30-32.
 #include "bn_moments.h"
+#include "env.h"
 #include "head.h"
 #include "pk2.h"
 
@@ -606,10 +607,7 @@ extern "C" int lbt_head_fwd_bwd(const lbt_head* h, void* stream) {
   // workgroups per sample: the pass A / un-pool split over up to LBT_HEAD_SPLIT pixel ranges (default 2;
   // 4 when 2 per sample leave the launch with fewer workgroups than CUs -- small per-GPU batches:
   // 17.0 -> 15.6 us at B=16)
-  static const int senv = [] {
-    const char* e = getenv("LBT_HEAD_SPLIT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int senv = getenv_int("LBT_HEAD_SPLIT", 0);
   const int smax = senv > 0 ? senv : (h->N * 2 < 256 ? 4 : 2);
   int S = smax;
   while (S > 1 && (h->HW % S || (int64_t)h->N * S > 0x7fffffff || (h->chain && kChainSlots % S))) --S;

@@ -19,9 +19,8 @@
 //        adds its exact int32 partial into shard (wg % nshard) of a zeroed slab[nshard][K][Cout]
 //        (integer atomics) for lbt_conv_wgrad_reduce(_many).
 #include "conv_epilogue.h"
+#include "env.h"
 #include "stem_bwd.h"
-
-#include <cstdlib>
 
 using namespace lbt;
 
@@ -533,7 +532,7 @@ extern "C" int lbt_conv_stem_fwd(const int16_t* x, const int8_t* w_hwio, lbt_con
   // whole-row bands of 16 rows (the CIFAR-10 stem of the fused plan) when they fill the chip: 10.5 vs 11.8 us
   // at B = 128 (256 bands), but 10.5 vs 5.6 us at B = 16 (32 bands: a band's serial 4-tile chain is the
   // launch), profiles/round6/stem_band.txt. LBT_STEM_BAND=0 / 1: never / always.
-  static const int band_env = getenv("LBT_STEM_BAND") ? atoi(getenv("LBT_STEM_BAND")) : -1;
+  static const int band_env = getenv_int("LBT_STEM_BAND", -1);
   const int64_t nband = (int64_t)d.N * (d.H / kSbRows);
   if ((band_env == 1 || (band_env < 0 && nband >= 256)) && yq && d.Cout == 16 && d.KH == 3 && d.KW == 3 &&
       d.SH == 1 && d.SW == 1 && d.PT == 1 && d.PL == 1 && d.Ho == d.H && d.Wo == d.W && d.W == kSbW &&

@@ -18,8 +18,7 @@
 // fp16 16x16x32 operand map (gfx950): lane l holds A[row l&15][k = 8*(l>>4) + j] and
 // B[k = 8*(l>>4) + j][col l&15], j = 0..7; C/D: col = l&15, row = 4*(l>>4) + reg.
 #include "dfxp_device.h"
-
-#include <cstdlib>
+#include "env.h"
 
 using namespace lbt;
 
@@ -576,8 +575,7 @@ extern "C" int lbt_conv_stem_wide_fwd(const int16_t* x, const int8_t* w_hwio, lb
   const int nct = d.Cout >= 64 ? 4 : d.Cout / 16;
   hipStream_t st = (hipStream_t)stream;
   // row tiles (default; LBT_STEM_WIDE_TILES=0 keeps the gather kernel below)
-  const char* tenv = getenv("LBT_STEM_WIDE_TILES");
-  const int tiles_env = tenv ? atoi(tenv) : 1;
+  const int tiles_env = getenv_int("LBT_STEM_WIDE_TILES", 1);
   if (tiles_env && d.Cin <= 4 && d.KW <= 8 && d.KH <= 15 && d.Wo <= kTilePixels && d.SH <= 16 && d.SW <= 16 &&
       !(reinterpret_cast<uintptr_t>(y) & 15)) {
     const int TR = d.Ho < kTilePixels / d.Wo ? d.Ho : kTilePixels / d.Wo;
@@ -587,10 +585,8 @@ extern "C" int lbt_conv_stem_wide_fwd(const int16_t* x, const int8_t* w_hwio, lb
     if (shm <= 65536 && R * Wimg <= kTilePre * kTileThreads && ntiles < 0x7fffffff) {
       // one round of resident workgroups (102 VGPRs: 2 per CU x 256 CUs), every one the same number
       // of tiles (ResNet-50 conv1, B=256: 512 -> 254 us, 768 -> 282, 1024 -> 257, 14336 -> ~590)
-      static const int64_t wgs = [] {
-        const char* e = getenv("LBT_STEM_WIDE_WGS");
-        return (int64_t)(e && atoi(e) > 0 ? atoi(e) : 512);
-      }();
+      static const int wgs_env = getenv_int("LBT_STEM_WIDE_WGS", 0);
+      const int64_t wgs = wgs_env > 0 ? wgs_env : 512;
       const int64_t per = (ntiles + wgs - 1) / wgs;
       dim3 grid((unsigned)((ntiles + per - 1) / per), (unsigned)((d.Cout + 63) / 64));
       switch (nct) {
@@ -648,18 +644,17 @@ extern "C" int lbt_conv_stem_wide_wgrad(const int16_t* x, int32_t x_bits, const 
   hipStream_t st = (hipStream_t)stream;
   // the row-chunk kernel where its LDS window fits (LBT_STEM_ROWS=0 at call time: never)
   {
-    const char* e = getenv("LBT_STEM_ROWS");
+    const int rows_env = getenv_int("LBT_STEM_ROWS", 1);
     const int xc = (d.Wo + kRwPx - 1) / kRwPx;
     const int64_t nchunks = (int64_t)d.N * d.Ho * xc;
     const int64_t cper = (nchunks + nsplit - 1) / nsplit;
-    if ((!e || atoi(e) != 0) && K <= 16 * kRwMaxKT && d.Cin <= kRwMaxCin && d.KH <= kRwMaxKH &&
+    if (rows_env != 0 && K <= 16 * kRwMaxKT && d.Cin <= kRwMaxCin && d.KH <= kRwMaxKH &&
         (kRwPx - 1) * d.SW + d.KW <= kRwMaxWC && d.Cout <= 64 && cper * kRwPx <= kMaxWgPixels &&
         d.KH * (((d.Wo < kRwPx ? d.Wo : kRwPx) - 1) * d.SW + d.KW) * d.Cin <= kRwWpt * 64 * kRwMaxKT) {
       // one group of up to 64 channels; LBT_STEM_CG=32 at call time: 32-channel groups on grid.y (half the
       // accumulators, two 10-wave workgroups per CU, but the window staged twice and 12 spilled registers:
       // 1296 vs 762 us at B=256, profiles/r05/stem_probe.txt)
-      const char* cgv = getenv("LBT_STEM_CG");
-      const int ncg = (d.Cout % 32 == 0 && cgv && atoi(cgv) == 32) ? d.Cout / 32 : 1;
+      const int ncg = (d.Cout % 32 == 0 && getenv_int("LBT_STEM_CG", 0) == 32) ? d.Cout / 32 : 1;
       const int rn = ncg > 1 ? 2 : nct;
 #define LBT_STEM_R(G, N)                                                                                  \
   hipLaunchKernelGGL((stem_wgrad_rows_kernel<G, N>), dim3((unsigned)nsplit, (unsigned)ncg), dim3(64 * kRwMaxKT), 0, st, \

@@ -283,7 +283,7 @@ class Conv2d_q(Layer_q):
         self.mfma = ops.mfma_ok(Cin, Cout) and bits <= 8 and grad_bits <= 8
         # x codes: unsigned 9-bit (offset int8, MFMA) / signed <= 8 bit (int8, MFMA) / int16 (VALU)
         # wide layers (channels beyond the register-resident MFMA kernels, or 16-bit gradients):
-        # LDS-tiled MFMA implicit GEMMs (igemm.hip) -- the weight gradient too when the input is a
+        # LDS-tiled MFMA implicit GEMMs (igemm*.hip) -- the weight gradient too when the input is a
         # post-ReLU 9-bit code (offset int8) and both channel counts are multiples of 64
         self.igemm_w = (not self.mfma and input_nonnegative and bits + 1 == 9 and Cin % 64 == 0
                         and Cout % 64 == 0)

@@ -722,7 +722,7 @@ def bn_bwd_b_wide(G, qng, qn, qn_q, ms, sums, n, dx, rows, C):
          stream())
 
 
-# ---------------------------------------------------------------- wide layers (igemm.hip)
+# ---------------------------------------------------------------- wide layers (igemm*.hip)
 def bn_bwd_a_wide_masked(g, y_mask, mask_r, qr, gb, gmask_out, qrg, R, qng, qn, gout, sums, rows, inner, C, g2=None,
                          y_bits=None):
     """y_bits: the ReLU mask as chain_fwd's ybits (one byte per channel quad) instead of fp32 y_mask."""
@@ -864,7 +864,7 @@ WGRAD3 = os.environ.get("LBT_WGRAD3", "1") != "0"
 
 
 def wgrad3_ok(d):
-    """lbt_conv_wgrad_igemm_store's all-taps 3x3 body takes this conv (wgrad3_ok in igemm.hip)."""
+    """lbt_conv_wgrad_igemm_store's all-taps 3x3 body takes this conv (wgrad3_ok in igemm_wgrad.hip)."""
     if not WGRAD3:
         return False
     if (d.KH, d.KW, d.SH, d.SW, d.PT, d.PB, d.PL, d.PR) != (3, 3, 1, 1, 1, 1, 1, 1) or d.Ho != d.H or d.Wo != d.W:
@@ -879,7 +879,7 @@ WGRAD1 = os.environ.get("LBT_WGRAD1", "1") != "0"
 
 def wgrad1_wci(d):
     """lbt_conv_wgrad_igemm_store's 1x1 body (16-bit G) takes this conv with (64 wci) x (256 / wci)
-    channel tiles (wgrad1_wci in igemm.hip); 0: not taken."""
+    channel tiles (wgrad1_wci in igemm_wgrad.hip); 0: not taken."""
     if not WGRAD1 or (d.KH, d.KW, d.PT, d.PL) != (1, 1, 0, 0) or d.PB < 0 or d.PR < 0:
         return 0
     if (d.Ho - 1) * d.SH >= d.H or (d.Wo - 1) * d.SW >= d.W:

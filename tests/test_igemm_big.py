@@ -1,4 +1,4 @@
-"""configs[3]'s production GEMM: the 256-row LDS-DMA implicit GEMM (igemm.hip igemm_big_kernel), which
+"""configs[3]'s production GEMM: the 256-row LDS-DMA implicit GEMM (igemm_big.hip igemm_big_kernel), which
 runs every large ResNet-50 forward and dgrad GEMM at the benched B=256.
 
 The kernel is taken only by GEMMs with >= 200 256-row tiles; ``ops.igemm_forced`` (the C-ABI
@@ -119,6 +119,36 @@ def test_big_dgrad_matches_generic(N, H, Cin, Cout, k, g_i16, add):
             ops.conv_dgrad_igemm(g, g_i16, wd, ksd, d, qg.desc, qw.desc, dx, add_src=addend)
         assert _launches() == n0 + 1, "the 256-row kernel did not run"
         assert torch.equal(dx, ref), (stages, max_bn, halo)
+
+
+@pytest.mark.parametrize("N,H,Cin,Cout,k", [
+    (2, 8, 16, 64, 1),    # 1x1 / 2: three of the four classes have no tap (dgrad_fill_class_kernel), one a 64 x 64 tile
+    (2, 9, 64, 64, 3),    # 3x3 / 2, pad 1: four classes of 4, 2, 2 and 1 taps, an odd image edge (5 / 4 rows)
+])
+@pytest.mark.parametrize("g_i16", [0, 1])
+@pytest.mark.parametrize("add", [False, True])
+def test_strided_dgrad_parity_classes_match_generic(N, H, Cin, Cout, k, g_i16, add):
+    """stride-2 dgrad: one launch per parity class of the dx pixels (igemm_kernel<..., CLS = true>, or the
+    fill kernel for a class no tap reaches), 8- and 16-bit gradient codes, with and without the residual
+    addend. Never the 256-row kernel, even when it is forced onto every shape."""
+    from lbt_amd.dfxp import ops
+    rng, ctx, (_, qw, qg), d, w_hwio, _, (wd, ksd), _ = _setup(N, H, Cin, Cout, k, 2, N * H + Cout + g_i16)
+    if g_i16:
+        g = torch.from_numpy(rng.integers(-32768, 32768, size=(N, d.Ho, d.Wo, Cout)).astype(np.int16)).to(DEV)
+    else:
+        g = torch.from_numpy(rng.integers(-128, 128, size=(N, d.Ho, d.Wo, Cout)).astype(np.int8)).to(DEV)
+    addend = torch.from_numpy(rng.normal(size=(N, H, H, Cin)).astype(np.float32)).to(DEV) if add else None
+    ref = torch.empty((N, H, H, Cin), device=DEV)
+    (ops.conv_dgrad_generic16 if g_i16 else ops.conv_dgrad_generic)(g, w_hwio, d, qg.desc, qw.desc, ref)
+    if add:
+        ref = ref + addend
+    assert ops.igemm_ok(Cout, Cin) and (d.SH, d.SW) == (2, 2)
+    dx = torch.full_like(ref, float("nan"))  # every pixel of every class has to be written
+    n0 = _launches()
+    with ops.igemm_forced(big=1, min_tiles=1):
+        ops.conv_dgrad_igemm(g, g_i16, wd, ksd, d, qg.desc, qw.desc, dx, add_src=addend)
+    assert _launches() == n0, "a strided dgrad ran on the 256-row kernel, not as parity classes"
+    assert torch.equal(dx, ref)
 
 
 @pytest.mark.parametrize("N,H,Cin,Cout,k", [(3, 14, 64, 128, 3), (2, 15, 128, 64, 1), (3, 14, 64, 256, 1)])

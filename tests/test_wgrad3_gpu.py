@@ -1,4 +1,4 @@
-"""The all-taps 3x3 weight gradient (igemm.hip wgrad3_kernel, behind lbt_conv_wgrad_igemm_store) against
+"""The all-taps 3x3 weight gradient (igemm_wgrad.hip wgrad3_kernel, behind lbt_conv_wgrad_igemm_store) against
 an exact float64 reference of dynamic_fixed_point.py:302's integer sum  dW[kh,kw,ci,co] =
 sum_{n,oh,ow} x[n, oh+kh-1, ow+kw-1, ci] * g[n, oh, ow, co]  (x = 0 outside the image; x offset int8
 codes x' = x - 128, g int16 or int8 codes). Bit-exact: every partial is an integer below 2^53."""
@@ -47,7 +47,7 @@ def test_wgrad3_exact(N, H, W, Ci, Co, g16):
                                          (2, 15, 128, 256, 2), (3, 7, 256, 128, 1), (4, 56, 64, 256, 1),
                                          (1, 8, 512, 512, 2)])
 def test_wgrad1_exact(N, H, Ci, Co, s):
-    """The 1x1 16-bit-gradient weight gradient (igemm.hip wgrad1_kernel: raw int16 G images read
+    """The 1x1 16-bit-gradient weight gradient (igemm_wgrad.hip wgrad1_kernel: raw int16 G images read
     transposed as (lo, hi) byte columns) against the float64 sum dW[ci, co] = sum_{n,oh,ow}
     x[n, oh*s, ow*s, ci] * g[n, oh, ow, co]; ragged pixel counts (P % 64 != 0), every tile shape
     (wci 1 / 2 / 4), strided shortcuts, several splits."""

@@ -34,7 +34,7 @@ def main():
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True,
                            text=True).stdout.splitlines()
     for r, n in zip(rows, names):
-        n = re.sub(r"\(anonymous namespace\)::", "", n)
+        n = re.sub(r"\(anonymous namespace\)::|lbt::", "", n)
         n = n.split("(")[0] if "(" in n and filt not in ("", "args") else n
         if filt and filt not in n:
             continue
