@@ -674,6 +674,19 @@ int lbt_dropout_bwd(const float* g, float* dx, int64_t n, float keep, const uint
  * (LBT_OUT_F32 -> LBT_EINVAL: float-mode layers run the separate launches). */
 int lbt_dropout_quantize(const float* x, void* out, int out_kind, int64_t rows, int64_t inner, float keep,
                          uint32_t did, int32_t relu, lbt_qdesc q, void* stream);
+/* The same three on a window of the mask stream: local element i takes the mask of element base + i,
+ * i.e. u_i above with base + i in place of i -- a rank's equal-sized shard of a global batch uses
+ * base = rank * n, so the shards of [N*b, ...] draw what one process draws on the whole tensor. The
+ * quantiser's noise (index mod inner) does not move. The entry points above are base = 0 of the same
+ * kernels. base >= 0 and base + n <= 2^34, else LBT_EINVAL (checked before any HIP call). A base that
+ * is no multiple of 4 takes one-element-per-thread kernels (for _quantize_at the generic kernel:
+ * the same codes and counter totals, another workgroup -> shard map). */
+int lbt_dropout_fwd_at(const float* x, float* y, int64_t n, int64_t base, float keep, const uint64_t* step,
+                       uint64_t seed, uint32_t did, int32_t relu, void* stream);
+int lbt_dropout_bwd_at(const float* g, float* dx, int64_t n, int64_t base, float keep, const uint64_t* step,
+                       uint64_t seed, uint32_t did, const float* relu_x, void* stream);
+int lbt_dropout_quantize_at(const float* x, void* out, int out_kind, int64_t rows, int64_t inner, int64_t base,
+                            float keep, uint32_t did, int32_t relu, lbt_qdesc q, void* stream);
 /* elementwise a + b (ResidualBlock_q :862 / :869). */
 int lbt_add(const float* a, const float* b, float* y, int64_t n, void* stream);
 /* AvgPool_q over the whole HxW map (:1017): y[n,c] = (sequential fp32 sum) * (1/(H*W)). */
@@ -759,6 +772,9 @@ int lbt_sgd_momentum(float* w, float* a, const float* g, int64_t n, float lr, fl
  * the grad quantiser's sharded per-channel sums chsum [LBT_NSHARD][2C] (:209, :459).       */
 int lbt_bias_add(float* y, const float* bq, int64_t n, int32_t C, void* stream);
 int lbt_bias_grad(const int64_t* chsum, int32_t C, lbt_qdesc qg, float* db, void* stream);
+/* The exact exchange's form (see lbt_xchg): num[c] = sum_shards chsum[k][c], the integer numerator of db,
+ * which lbt_step_finish dequantises as an lbt_fseg of kind 2 with qg = the layer's grad quantiser. */
+int lbt_bias_grad_x(const int64_t* chsum, int32_t C, int64_t* num, void* stream);
 
 /* ---------------------------------------------------------------- batched (one launch per step)
  * Job arrays live in DEVICE memory (uploaded once by the caller); grid.y = job index.          */
@@ -994,7 +1010,8 @@ int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* p, void* stream);
 
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
- * frozen chain used to return LBT_EINVAL.                                                        */
+ * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at and lbt_bias_grad_x are additions under the
+ * same number: every earlier signature and result stands.                                        */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

@@ -279,6 +279,9 @@ _SIGS = {
     "lbt_dropout_fwd": [_P, _P, c_int64, c_float, _P, c_uint64, c_uint32, c_int32, _P],
     "lbt_dropout_bwd": [_P, _P, c_int64, c_float, _P, c_uint64, c_uint32, _P, _P],
     "lbt_dropout_quantize": [_P, _P, c_int32, c_int64, c_int64, c_float, c_uint32, c_int32, QDesc, _P],
+    "lbt_dropout_fwd_at": [_P, _P, c_int64, c_int64, c_float, _P, c_uint64, c_uint32, c_int32, _P],
+    "lbt_dropout_bwd_at": [_P, _P, c_int64, c_int64, c_float, _P, c_uint64, c_uint32, _P, _P],
+    "lbt_dropout_quantize_at": [_P, _P, c_int32, c_int64, c_int64, c_int64, c_float, c_uint32, c_int32, QDesc, _P],
     "lbt_add": [_P, _P, _P, c_int64, _P],
     "lbt_maxpool_fwd": [_P, _P, _P, ConvDesc, _P],
     "lbt_maxpool_bwd": [_P, _P, _P, ConvDesc, _P],
@@ -301,6 +304,7 @@ _SIGS = {
     "lbt_sgd_momentum": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P],
     "lbt_bias_add": [_P, _P, c_int64, c_int32, _P],
     "lbt_bias_grad": [_P, c_int32, QDesc, _P, _P],
+    "lbt_bias_grad_x": [_P, c_int32, _P, _P],
     "lbt_dfxp_quantize_weights": [_P, c_int32, c_int32, _P],
     "lbt_dfxp_quantize_many": [_P, c_int32, _P],
     "lbt_dfxp_noise_fill": [_P, c_int32, c_int64, _P, c_int64, _P],

@@ -3,13 +3,18 @@
 //  lbt_dropout_fwd       y  = fl32(x / keep) * mask, optionally on max(x, 0)
 //  lbt_dropout_bwd       dx = fl32(g / keep) * mask, the mask regenerated from its counter
 //  lbt_dropout_quantize  dropout + the next layer's input quantiser in one pass: 4 B in, 1-2 B out
+//  lbt_dropout_*_at      the same three on a window of the stream: local element i draws the mask of
+//                        element base + i (a rank's shard of the global batch); the plain entry points
+//                        are base = 0
 //
 // The mask of element i of the whole tensor (batch included: tf.nn.dropout draws x.shape noise) is
 //   u_i = Philox4x32-10((i >> 2, did, step_lo, step_hi), (seed_lo, seed_hi))[i & 3] >> 8, times 2^-24
 //   m_i = fl32(keep + u_i) >= 1
 // on the Philox stream of the quantisers (dfxp_device.h), keyed by the layer's id `did` where they
 // use their range variable's. One thread owns four consecutive elements: one Philox call, one
-// 16-byte load and one store. All three are HBM-bound streaming passes.
+// 16-byte load and one store. All three are HBM-bound streaming passes. A base that is no multiple
+// of 4 puts a thread's four elements across two Philox blocks: those launches take the per-element
+// kernels (one Philox call per element).
 #include "dfxp_device.h"
 
 using namespace lbt;
@@ -29,11 +34,12 @@ LBT_DEV float drop1(float x, float keep, float u, int relu) {
 
 __global__ __launch_bounds__(kThreads) void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                int64_t n, float keep, const uint64_t* __restrict__ step,
-                                                               uint64_t seed, uint32_t did, int relu, int vec) {
+                                                               uint64_t seed, uint32_t did, int relu, int vec,
+                                                               int64_t blk0) {
   const int64_t blk = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const int64_t i = blk << 2;
   if (i >= n) return;
-  const Noise4 u = noise4((uint64_t)blk, did, step[0], seed);
+  const Noise4 u = noise4((uint64_t)(blk0 + blk), did, step[0], seed);  // blk0 = base / 4
   if (vec && i + 4 <= n) {
     const float4 v = *reinterpret_cast<const float4*>(x + i);
     float4 o;
@@ -47,6 +53,16 @@ __global__ __launch_bounds__(kThreads) void dropout_fwd_kernel(const float* __re
   }
 }
 
+// base % 4 != 0: one element per thread, its own Philox call at the global index base + i
+__global__ __launch_bounds__(kThreads) void dropout_fwd_elem_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                    int64_t n, float keep,
+                                                                    const uint64_t* __restrict__ step, uint64_t seed,
+                                                                    uint32_t did, int relu, int64_t base) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  y[i] = drop1(x[i], keep, noise1((uint64_t)(base + i), did, step[0], seed), relu);
+}
+
 // relu_x: the input of a ReLU folded in front (lbt_dropout_fwd's relu = 1) -- its mask on top, as
 // relu_bwd_kernel applies it (g where x > 0, else +0)
 LBT_DEV float drop_bwd1(float g, float keep, float u, bool has_rx, float rx) {
@@ -57,11 +73,12 @@ LBT_DEV float drop_bwd1(float g, float keep, float u, bool has_rx, float rx) {
 __global__ __launch_bounds__(kThreads) void dropout_bwd_kernel(const float* __restrict__ g, float* __restrict__ dx,
                                                                int64_t n, float keep, const uint64_t* __restrict__ step,
                                                                uint64_t seed, uint32_t did,
-                                                               const float* __restrict__ relu_x, int vec) {
+                                                               const float* __restrict__ relu_x, int vec,
+                                                               int64_t blk0) {
   const int64_t blk = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const int64_t i = blk << 2;
   if (i >= n) return;
-  const Noise4 u = noise4((uint64_t)blk, did, step[0], seed);
+  const Noise4 u = noise4((uint64_t)(blk0 + blk), did, step[0], seed);
   const bool rx = relu_x != nullptr;
   if (vec && i + 4 <= n) {
     const float4 v = *reinterpret_cast<const float4*>(g + i);
@@ -78,14 +95,26 @@ __global__ __launch_bounds__(kThreads) void dropout_bwd_kernel(const float* __re
   }
 }
 
+__global__ __launch_bounds__(kThreads) void dropout_bwd_elem_kernel(const float* __restrict__ g, float* __restrict__ dx,
+                                                                    int64_t n, float keep,
+                                                                    const uint64_t* __restrict__ step, uint64_t seed,
+                                                                    uint32_t did, const float* __restrict__ relu_x,
+                                                                    int64_t base) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const bool rx = relu_x != nullptr;
+  dx[i] = drop_bwd1(g[i], keep, noise1((uint64_t)(base + i), did, step[0], seed), rx, rx ? relu_x[i] : 0.f);
+}
+
 // quantize_rows_kernel (quantize.hip) with dropout applied to each element on its way in: the same
 // grid, rows per thread, counter reduction and shard per workgroup, so the codes AND every counter
 // shard equal lbt_dropout_fwd followed by lbt_dfxp_quantize. The quantiser's noise is per column
 // group (index mod inner: once per thread), the dropout's per element of the whole tensor (one
-// Philox call per row: inner % 4 == 0 keeps a thread's four elements inside one Philox block).
+// Philox call per row: inner % 4 == 0 and gbase % 4 == 0 keep a thread's four elements inside one
+// Philox block). gbase: the global index of local element 0.
 __global__ __launch_bounds__(kThreads) void dropout_quantize_rows_kernel(
     const float* __restrict__ x, void* __restrict__ out, int out_kind, int64_t rows, int64_t inner, int rpt,
-    float keep, uint32_t did, int relu, lbt_qdesc q) {
+    float keep, uint32_t did, int relu, lbt_qdesc q, int64_t gbase) {
   __shared__ int sh_cnt[2 * kThreads / 64];
   const QState s = qstate(q);
   const int64_t groups = inner >> 2;
@@ -100,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void dropout_quantize_rows_kernel(
     for (int64_t r = r0; r < rend; ++r) {
       const int64_t base = r * inner + (g << 2);
       const float4 v = *reinterpret_cast<const float4*>(x + base);
-      const Noise4 u = noise4((uint64_t)(base >> 2), did, s.step, q.seed);
+      const Noise4 u = noise4((uint64_t)((gbase + base) >> 2), did, s.step, q.seed);
       int c[4];
       c[0] = quant1(s, q.stochastic, drop1(v.x, keep, u.u[0], relu), n.u[0], ov1, ov2);
       c[1] = quant1(s, q.stochastic, drop1(v.y, keep, u.u[1], relu), n.u[1], ov1, ov2);
@@ -130,12 +159,12 @@ __global__ __launch_bounds__(kThreads) void dropout_quantize_rows_kernel(
 // Any shape (quantize_generic_kernel's grid): one element per thread, per-element Philox for both.
 __global__ __launch_bounds__(kThreads) void dropout_quantize_generic_kernel(
     const float* __restrict__ x, void* __restrict__ out, int out_kind, int64_t n, int64_t inner, float keep,
-    uint32_t did, int relu, lbt_qdesc q) {
+    uint32_t did, int relu, lbt_qdesc q, int64_t gbase) {
   __shared__ int sh_cnt[2 * kThreads / 64];
   const QState s = qstate(q);
   int ov1 = 0, ov2 = 0;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-    const float ud = noise1((uint64_t)i, did, s.step, q.seed);
+    const float ud = noise1((uint64_t)(gbase + i), did, s.step, q.seed);
     const float u = q.stochastic ? qnoise1(q, s.step, i % inner) : 0.f;
     const int c = quant1(s, q.stochastic, drop1(x[i], keep, ud, relu), u, ov1, ov2);
     store_code(out, out_kind, i, c, s.inv_m);
@@ -144,44 +173,71 @@ __global__ __launch_bounds__(kThreads) void dropout_quantize_generic_kernel(
 }
 
 bool keep_ok(float keep) { return keep > 0.f && keep <= 1.f; }  // false for NaN
+// the window [base, base + n) lies inside the stream's 2^34 elements
+bool window_ok(int64_t base, int64_t n) { return n >= 0 && base >= 0 && n <= kMaxN && base <= kMaxN - n; }
 
 }  // namespace
 
-extern "C" int lbt_dropout_fwd(const float* x, float* y, int64_t n, float keep, const uint64_t* step, uint64_t seed,
-                               uint32_t did, int32_t relu, void* stream) {
-  if (n < 0 || n > kMaxN || !keep_ok(keep) || !step) return LBT_EINVAL;
+extern "C" int lbt_dropout_fwd_at(const float* x, float* y, int64_t n, int64_t base, float keep, const uint64_t* step,
+                                  uint64_t seed, uint32_t did, int32_t relu, void* stream) {
+  if (!window_ok(base, n) || !keep_ok(keep) || !step) return LBT_EINVAL;
   if (n == 0) return LBT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (base & 3) {
+    const int64_t blocks = (n + kThreads - 1) / kThreads;  // <= 2^26
+    hipLaunchKernelGGL(dropout_fwd_elem_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, y, n, keep, step,
+                       seed, did, relu != 0, base);
+    return (int)hipGetLastError();
+  }
   const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   const int64_t blocks = ((n + 3) / 4 + kThreads - 1) / kThreads;  // <= 2^24
-  hipLaunchKernelGGL(dropout_fwd_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, x, y, n, keep,
-                     step, seed, did, relu != 0, vec);
+  hipLaunchKernelGGL(dropout_fwd_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, y, n, keep, step, seed, did,
+                     relu != 0, vec, base >> 2);
+  return (int)hipGetLastError();
+}
+
+extern "C" int lbt_dropout_fwd(const float* x, float* y, int64_t n, float keep, const uint64_t* step, uint64_t seed,
+                               uint32_t did, int32_t relu, void* stream) {
+  return lbt_dropout_fwd_at(x, y, n, 0, keep, step, seed, did, relu, stream);
+}
+
+extern "C" int lbt_dropout_bwd_at(const float* g, float* dx, int64_t n, int64_t base, float keep, const uint64_t* step,
+                                  uint64_t seed, uint32_t did, const float* relu_x, void* stream) {
+  if (!window_ok(base, n) || !keep_ok(keep) || !step) return LBT_EINVAL;
+  if (n == 0) return LBT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (base & 3) {
+    const int64_t blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(dropout_bwd_elem_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, g, dx, n, keep, step,
+                       seed, did, relu_x, base);
+    return (int)hipGetLastError();
+  }
+  const int vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
+                    reinterpret_cast<uintptr_t>(relu_x)) & 15) == 0;
+  const int64_t blocks = ((n + 3) / 4 + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, g, dx, n, keep, step, seed, did,
+                     relu_x, vec, base >> 2);
   return (int)hipGetLastError();
 }
 
 extern "C" int lbt_dropout_bwd(const float* g, float* dx, int64_t n, float keep, const uint64_t* step, uint64_t seed,
                                uint32_t did, const float* relu_x, void* stream) {
-  if (n < 0 || n > kMaxN || !keep_ok(keep) || !step) return LBT_EINVAL;
-  if (n == 0) return LBT_OK;
-  const int vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
-                    reinterpret_cast<uintptr_t>(relu_x)) & 15) == 0;
-  const int64_t blocks = ((n + 3) / 4 + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, g, dx, n, keep,
-                     step, seed, did, relu_x, vec);
-  return (int)hipGetLastError();
+  return lbt_dropout_bwd_at(g, dx, n, 0, keep, step, seed, did, relu_x, stream);
 }
 
-extern "C" int lbt_dropout_quantize(const float* x, void* out, int out_kind, int64_t rows, int64_t inner, float keep,
-                                    uint32_t did, int32_t relu, lbt_qdesc q, void* stream) {
-  if (rows < 0 || inner < 0 || !keep_ok(keep)) return LBT_EINVAL;
+extern "C" int lbt_dropout_quantize_at(const float* x, void* out, int out_kind, int64_t rows, int64_t inner,
+                                       int64_t base, float keep, uint32_t did, int32_t relu, lbt_qdesc q,
+                                       void* stream) {
+  if (rows < 0 || inner < 0 || base < 0 || base > kMaxN || !keep_ok(keep)) return LBT_EINVAL;
   if (out_kind != LBT_OUT_I8 && out_kind != LBT_OUT_U8OFF && out_kind != LBT_OUT_I16) return LBT_EINVAL;
   if (q.bits < 1 || q.bits > 16) return LBT_EINVAL;
   if ((out_kind == LBT_OUT_I8 && q.bits > 8) || (out_kind == LBT_OUT_U8OFF && q.bits > 9)) return LBT_EINVAL;
   if (rows == 0 || inner == 0) return LBT_OK;
-  if (rows > kMaxN / inner) return LBT_EINVAL;  // n > 2^34
+  if (rows > (kMaxN - base) / inner) return LBT_EINVAL;  // base + n > 2^34
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = rows * inner;
   // the two paths, grids and rows per thread of lbt_dfxp_quantize: the same workgroup -> shard map
-  const bool vec = (inner % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (inner >= 64);
+  const bool vec = (inner % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (inner >= 64) && !(base & 3);
   if (vec) {
     const int64_t groups = inner / 4;
     const int64_t gblocks = (groups + kThreads - 1) / kThreads;
@@ -191,12 +247,17 @@ extern "C" int lbt_dropout_quantize(const float* x, void* out, int out_kind, int
     const int64_t yblocks = (rows + rpt - 1) / rpt;
     if (yblocks > 65535) return LBT_EINVAL;
     hipLaunchKernelGGL(dropout_quantize_rows_kernel, dim3((unsigned)gblocks, (unsigned)yblocks), dim3(kThreads), 0, st,
-                       x, out, out_kind, rows, inner, (int)rpt, keep, did, relu != 0, q);
+                       x, out, out_kind, rows, inner, (int)rpt, keep, did, relu != 0, q, base);
   } else {
     int64_t blocks = (n + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(dropout_quantize_generic_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, out,
-                       out_kind, n, inner, keep, did, relu != 0, q);
+                       out_kind, n, inner, keep, did, relu != 0, q, base);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int lbt_dropout_quantize(const float* x, void* out, int out_kind, int64_t rows, int64_t inner, float keep,
+                                    uint32_t did, int32_t relu, lbt_qdesc q, void* stream) {
+  return lbt_dropout_quantize_at(x, out, out_kind, rows, inner, 0, keep, did, relu, q, stream);
 }

@@ -127,6 +127,16 @@ __global__ void bias_grad_kernel(const int64_t* __restrict__ chsum, int C, lbt_q
   db[c] = (float)((double)s * ldexp(1.0, -frac_exp(qg)));
 }
 
+// The exact exchange's form: num[c] = sum_shards S1[c], the integer that bias_grad_kernel dequantises
+// (lbt_step_finish's kind 2 applies the same formula to the all-reduced sum).
+__global__ void bias_grad_x_kernel(const int64_t* __restrict__ chsum, int C, long long* __restrict__ num) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  long long s = 0;
+  for (int k = 0; k < LBT_NSHARD; ++k) s += chsum[(int64_t)k * 2 * C + c];
+  num[c] = s;
+}
+
 unsigned blocks4(int64_t n) { return (unsigned)(((n + 3) / 4 + 255) / 256); }
 
 // bitwise comparison of div_by(x, recip(y)) with the compiler's correctly rounded x / y
@@ -195,6 +205,12 @@ extern "C" int lbt_bias_add(float* y, const float* b, int64_t n, int32_t C, void
 }
 extern "C" int lbt_bias_grad(const int64_t* chsum, int32_t C, lbt_qdesc qg, float* db, void* stream) {
   hipLaunchKernelGGL(bias_grad_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, chsum, C, qg, db);
+  return (int)hipGetLastError();
+}
+extern "C" int lbt_bias_grad_x(const int64_t* chsum, int32_t C, int64_t* num, void* stream) {
+  if (!chsum || !num || C <= 0) return LBT_EINVAL;
+  hipLaunchKernelGGL(bias_grad_x_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, chsum, C,
+                     (long long*)num);
   return (int)hipGetLastError();
 }
 

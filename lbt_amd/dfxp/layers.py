@@ -1446,6 +1446,8 @@ class Dropout_q(Layer_q):
     the quantisers' Philox stream under this layer's id (``qid_of(name)``; the reference's layer has
     no name: ``dropout%d`` in construction order within the context) -- DESIGN section 4. No mask is
     kept: the backward regenerates it from the same counter, so both must run at the same step.
+    Inside a data-parallel Trainer's training step on a context that declares its rank, i is the index
+    in the GLOBAL batch's tensor (``ctx.mask_base``: this rank's shard starts at ``rank * X.numel()``).
 
     Wiring (what a model builder sets; ``LBT_DROPOUT_FUSE=0`` ignores it):
     ``drop.feeds = next_layer`` (a Conv2d_q / Dense_q): forward returns X untouched and that layer

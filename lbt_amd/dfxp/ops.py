@@ -517,9 +517,14 @@ def dropout_fwd(x, y, keep, ctx, did, relu=False):
     `did` at ctx's step and seed; relu: on max(x, 0) (a ReLU_q folded in front)."""
     _check(x, torch.float32, "x")
     _check(y, torch.float32, "y")
+    base = ctx.mask_base(x.numel())  # a rank's shard inside the data-parallel training step, else None
     with _Timed("dropout_fwd_kernel", x.numel() * 8):
-        call("lbt_dropout_fwd", ptr(x), ptr(y), x.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
-             1 if relu else 0, stream())
+        if base is not None:
+            call("lbt_dropout_fwd_at", ptr(x), ptr(y), x.numel(), base, float(keep), ptr(ctx.step), ctx.seed,
+                 int(did), 1 if relu else 0, stream())
+        else:
+            call("lbt_dropout_fwd", ptr(x), ptr(y), x.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
+                 1 if relu else 0, stream())
     return y
 
 
@@ -531,9 +536,14 @@ def dropout_bwd(g, dx, keep, ctx, did, relu_x=None):
         _check(relu_x, torch.float32, "relu_x")
         if relu_x.numel() != g.numel():
             raise ValueError("relu_x has %d elements, the gradient %d" % (relu_x.numel(), g.numel()))
+    base = ctx.mask_base(g.numel())
     with _Timed("dropout_bwd_kernel", g.numel() * (8 if relu_x is None else 12)):
-        call("lbt_dropout_bwd", ptr(g), ptr(dx), g.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
-             ptr(relu_x), stream())
+        if base is not None:
+            call("lbt_dropout_bwd_at", ptr(g), ptr(dx), g.numel(), base, float(keep), ptr(ctx.step), ctx.seed,
+                 int(did), ptr(relu_x), stream())
+        else:
+            call("lbt_dropout_bwd", ptr(g), ptr(dx), g.numel(), float(keep), ptr(ctx.step), ctx.seed, int(did),
+                 ptr(relu_x), stream())
     return dx
 
 
@@ -547,11 +557,16 @@ def dropout_quantize(x, keep, did, q, kind, out=None, relu=False, desc=None):
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype(kind), device=x.device)
     q.observe(x.numel())
-    vec = inner % 4 == 0 and inner >= 64 and x.data_ptr() % 16 == 0
+    base = q.ctx.mask_base(x.numel())
+    vec = inner % 4 == 0 and inner >= 64 and x.data_ptr() % 16 == 0 and not (base or 0) % 4
     with _Timed("dropout_quantize_rows_kernel" if vec else "dropout_quantize_generic_kernel",
                 x.numel() * (4 + _code_bytes(kind))):
-        call("lbt_dropout_quantize", ptr(x), ptr(out), kind, rows, inner, float(keep), int(did), 1 if relu else 0,
-             q.desc if desc is None else desc, stream())
+        if base is not None:
+            call("lbt_dropout_quantize_at", ptr(x), ptr(out), kind, rows, inner, base, float(keep), int(did),
+                 1 if relu else 0, q.desc if desc is None else desc, stream())
+        else:
+            call("lbt_dropout_quantize", ptr(x), ptr(out), kind, rows, inner, float(keep), int(did),
+                 1 if relu else 0, q.desc if desc is None else desc, stream())
     return out
 
 
@@ -626,6 +641,10 @@ def bias_add(y, bq, C):
 
 
 def bias_grad(chsum, C, qg, db):
+    num = _num(db)
+    if num is not None:  # exact exchange: the integer numerator (lbt_step_finish dequantises the global sum)
+        call("lbt_bias_grad_x", ptr(chsum), int(C), num, stream())
+        return
     call("lbt_bias_grad", ptr(chsum), int(C), qg, ptr(db), stream())
 
 

@@ -20,8 +20,14 @@ buffer, the softmax (lbt_softmax_xent_n) normalises by the global batch and leav
 loss slot, and lbt_step_reduce_x's fold blocks add the counters: an N-rank step equals the oracle's
 N-shard step bit for bit (tests/test_dp_resnet50_gpu.py).
 
-Other layer-wise models (fp32-mode layers, biases) exchange dequantised gradients instead, an
-all-reduce SUM of
+A context that declares its rank (DfxpContext(world_size=N, rank=r)) extends this to the biased plain
+models with Dropout_q: a bias gradient travels as its numerator too (lbt_bias_grad_x, an lbt_fseg of kind
+2), and inside the training step each dropout layer draws the mask bits of its shard's elements of the
+GLOBAL tensor (base = rank * n: lbt_dropout_*_at), so the N-rank step equals the one-process step on the
+whole batch bit for bit (tests/test_dp_dropout_gpu.py).
+
+Other layer-wise models (fp32-mode layers; biases without a declared rank) exchange dequantised
+gradients instead, an all-reduce SUM of
 
     [ flat fp32 gradients | every quantiser's folded overflow counters ]
 
@@ -72,7 +78,7 @@ def make_exchange(n_grads, n_slots, device):
 
 
 def finish_segments(flat, device):
-    """lbt_fseg per parameter tensor of a FlatParams (kind 0 conv / dense W, 1 gamma, 2 beta) as a
+    """lbt_fseg per parameter tensor of a FlatParams (kind 0 conv / dense W, 1 gamma, 2 beta / bias) as a
     device array (raw bytes), and the finish kernel's block count."""
     from . import _lib
     from .dfxp import ops
@@ -82,7 +88,7 @@ def finish_segments(flat, device):
             kind, qx, qg = 0, owner.X_range.desc, owner.grad_range.desc
         elif var == "gamma":
             kind, qx, qg = 1, owner.X_range.desc, owner.grad_range.desc
-        elif var == "beta":
+        elif var in ("beta", "b"):  # a Conv2d_q / Dense_q bias: lbt_bias_grad's formula is beta's
             kind, qx, qg = 2, owner.X_range.desc, owner.grad_range.desc
         else:
             raise NotImplementedError("exact exchange of parameter %r" % var)
@@ -92,14 +98,22 @@ def finish_segments(flat, device):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device), blocks
 
 
-def exact_layerwise_ok(model):
+def exact_layerwise_ok(model, biases=False):
     """True when every trainable variable of a layer-wise model gets an INTEGER gradient numerator
     (quantised conv / dense W, BN gamma / beta; no fp32-mode layer, no bias): the models the exact
-    int64 exchange (ops.set_exchange_sink) takes."""
+    int64 exchange (ops.set_exchange_sink) takes. biases=True also accepts Conv2d_q / Dense_q biases
+    (lbt_bias_grad_x): what the Trainer asks when the context declares its rank."""
+    return float_mode_layer(model, biases) is None
+
+
+def float_mode_layer(model, biases=True):
+    """The first parameter owner the exact exchange cannot take (a float-mode layer, a variable that is
+    none of W / gamma / beta / -- with biases -- b), or None."""
+    ok = ("W", "gamma", "beta") + (("b",) if biases else ())
     for owner, var, _ in model.param_slots():
-        if var not in ("W", "gamma", "beta") or getattr(owner, "fmode", False):
-            return False
-    return True
+        if var not in ok or getattr(owner, "fmode", False):
+            return owner
+    return None
 
 
 def allreduce_comm(comm, group=None):

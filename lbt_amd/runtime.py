@@ -68,11 +68,19 @@ class Quantizer:
 
 
 class DfxpContext:
-    def __init__(self, device="cuda", capacity=1024, seed=0, world_size=1, sums_capacity=1 << 24):
+    def __init__(self, device="cuda", capacity=1024, seed=0, world_size=1, sums_capacity=1 << 24, rank=None):
+        """rank: this process's position among world_size equal batch shards (None: not declared). A
+        declared rank lets the data-parallel Trainer train Dropout_q models: inside its training step
+        (``shard_masks``) a dropout input of n local elements draws the mask bits of elements
+        [rank*n, (rank+1)*n) of the global tensor (``mask_base``)."""
         self.device = torch.device(device)
         self.capacity = capacity
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.world_size = int(world_size)
+        if rank is not None and not 0 <= int(rank) < self.world_size:
+            raise ValueError("rank %r outside [0, world_size = %d)" % (rank, self.world_size))
+        self.rank = None if rank is None else int(rank)
+        self._shard_masks = False
         dev = self.device
         self.exps = torch.zeros(capacity, dtype=torch.int32, device=dev)
         self.counts = torch.zeros(capacity * NSHARD * CSTRIDE, dtype=torch.int32, device=dev)
@@ -90,6 +98,18 @@ class DfxpContext:
         self._extra_arenas = []
         self.sums_managed = False
         self.params_ready = False  # a model's batched prologue quantised every participating parameter  # True while a Trainer zeroes the arena once per step
+
+    def shard_masks(self):
+        """Context manager the data-parallel Trainer holds around a training step's forward and backward:
+        inside it ``mask_base`` is the shard's offset, outside it (evaluation, a single process) 0."""
+        return _ShardMasks(self)
+
+    def mask_base(self, numel):
+        """Global index of local element 0 of a dropout input of numel elements: rank * numel inside
+        ``shard_masks`` on a context that declares its rank, else None (the plain entry points)."""
+        if not self._shard_masks or self.rank is None:
+            return None
+        return self.rank * int(numel)
 
     def quantizer(self, name, bits, initial=2, target=0.0, stochastic=True):
         """Register a quantiser (a ``*_range`` variable initialised to ``initial``)."""
@@ -224,6 +244,19 @@ class DfxpContext:
             raise ValueError("quantiser layout mismatch")
         self.exps.copy_(sd["exps"])
         self.step.copy_(sd["step"])
+
+
+class _ShardMasks:
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __enter__(self):
+        self.prev, self.ctx._shard_masks = self.ctx._shard_masks, True
+        return self.ctx
+
+    def __exit__(self, et, ev, tb):
+        self.ctx._shard_masks = self.prev
+        return False
 
 
 _default = None

@@ -21,6 +21,9 @@ MI355X-native execution:
     samples is bit-identical to one process on the N*b batch.
   - layer-wise models: dequantised fp32 gradients + counters folded into exact fp32 pairs, one
     fp32 all-reduce (gscale = 1/world).
+  - ``DfxpContext(world_size=N, rank=r)``: the plain models with ``Dropout_q`` train data-parallel on
+    the exact int64 exchange (bias numerators included), each rank drawing its shard's bits of the
+    global batch's dropout mask: N ranks on the shards equal one process on the whole batch.
 """
 import os
 import sys
@@ -89,16 +92,30 @@ class Trainer:
             capture_comm = (dist_on and dist.get_backend(process_group) == "nccl"
                             and os.environ.get("LBT_CAPTURE_COMM", "1") == "1")
         self.capture_comm = bool(capture_comm) and dist_on
+        # a context that declares its rank: shard-aware dropout masks and the exact exchange with biases
+        ranked = self.ctx.rank is not None
+        if ranked and dist_on and self.ctx.rank != dist.get_rank(process_group):
+            raise ValueError("DfxpContext.rank (%d) must equal this process's rank in the group (%d)"
+                             % (self.ctx.rank, dist.get_rank(process_group)))
         if self.dp and self._has_dropout(model):
-            # every rank would draw the same mask (the noise keys do not depend on the rank): the
-            # shards of one global batch need per-rank mask streams, which are not defined yet
-            raise NotImplementedError("data-parallel training of a model with Dropout_q layers is not "
-                                      "supported: per-rank dropout mask streams are not implemented")
+            if not ranked:
+                # every rank would draw the same mask (the noise keys do not depend on the rank): the
+                # shards of one global batch need the context to say where its shard sits
+                raise NotImplementedError("data-parallel training of a model with Dropout_q layers needs the "
+                                          "shard position: DfxpContext(world_size=N, rank=r)")
+            bad = D.float_mode_layer(model) if not hasattr(model, "set_exchange") else None
+            if bad is not None:
+                # bit-equality with the one-process step rests on integer numerators
+                raise NotImplementedError("data-parallel training of a model with Dropout_q layers takes "
+                                          "integer-coded layers only: %r is a float-mode layer (its gradients "
+                                          "are no integer numerators)" % getattr(bad, "name", bad))
         exact = self.dp and hasattr(model, "set_exchange")
         # layer-wise models (ResNet-50, configs[3]): the same exact int64 exchange when every gradient
-        # is an integer numerator (integer-coded W / gamma / beta only; LBT_EXACT_LAYERWISE=0: fp32)
-        self._lw_exact = (self.dp and not exact and D.exact_layerwise_ok(model)
-                          and os.environ.get("LBT_EXACT_LAYERWISE", "1") == "1")
+        # is an integer numerator (integer-coded W / gamma / beta, and with a declared rank biases;
+        # LBT_EXACT_LAYERWISE=0: fp32 -- not with Dropout_q, whose guarantee is the exact exchange's)
+        self._lw_exact = (self.dp and not exact and D.exact_layerwise_ok(model, biases=ranked)
+                          and (os.environ.get("LBT_EXACT_LAYERWISE", "1") == "1"
+                               or (ranked and self._has_dropout(model))))
         if self.dp and not exact and not self._lw_exact:
             n = sum(getattr(o, v).numel() for o, v, _ in model.param_slots())
             self.comm = D.make_comm_buffer(n, len(self.ctx.quantizers), self.ctx.device)
@@ -216,9 +233,10 @@ class Trainer:
             self._loss_n = int(X.shape[0]) * self.world
             ops.set_exchange_sink(self.flat.g, self.flat.n, self.xbuf, x.loss_off, self.world)
             try:
-                m.forward(X)
-                m.compute_loss(y)
-                m.backward()
+                with self.ctx.shard_masks():  # Dropout_q: this rank's bits of the global batch's mask
+                    m.forward(X)
+                    m.compute_loss(y)
+                    m.backward()
             finally:
                 ops.set_exchange_sink()
             # the overflow counters into the buffer (lbt_step_reduce_x with its fold blocks only)
