@@ -81,7 +81,9 @@ typedef struct lbt_conv_desc {
  * out is written in `out_kind` encoding, same element order as x.  If chsum != NULL the
  * per-channel integer sums S1[c] = sum q, S2[c] = sum q^2 over all elements with channel
  * c = index % C are ADDED to the sharded int64 buffer chsum[LBT_NSHARD][2C] (S1 at [0,C),
- * S2 at [C,2C) of a shard).  All "chsum"/"sums" buffers below use that sharded layout.   */
+ * S2 at [C,2C) of a shard), exactly for every out_kind at 1..16 bits (9..16-bit codes: q^2 summed in 64
+ * bits); chsum with more than 16 bits is LBT_EINVAL.
+ * All "chsum"/"sums" buffers below use that sharded layout.                               */
 int lbt_dfxp_quantize(const float* x, void* out, int out_kind, int64_t rows, int64_t inner,
                       lbt_qdesc q, int64_t* chsum, int32_t C, void* stream);
 
@@ -135,7 +137,7 @@ int lbt_dfxp_quantize_weight(const float* w, int32_t KH, int32_t KW, int32_t Cin
  * Epilogue: acc -> fp32 * 2^-(ex+ew); written to y (fp32 NHWC) if y != NULL and/or
  * quantised with qout into yq (int8 NHWC) with per-channel sums into ychsum; a stochastic
  * qout must carry its noise table (qout.noise, lbt_dfxp_noise_fill), else LBT_EINVAL.
- * Requires Cin % 16 == 0 and Cout % 16 == 0.                                               */
+ * Requires Cin % 16 == 0 and Cout % 16 == 0; qout of at most 8 bits (int8 codes, int32 lane sums of q^2). */
 int lbt_conv_fwd_i8(const int8_t* xq, int32_t x_u8off, const int8_t* wf, int32_t ksf,
                     const int32_t* wcolsum, lbt_conv_desc d, lbt_qdesc qx, lbt_qdesc qw,
                     float* y, int8_t* yq, lbt_qdesc qout, int64_t* ychsum, void* stream);
@@ -471,7 +473,7 @@ int lbt_conv_dgrad_chain_wgrad_i8w4(const int8_t* gq, const uint8_t* wd4, int32_
  *   mg = sg*SG/n, mgx = sg*(s*SGQ - mu*SG)/(n*sigma)   (double -> fp32)
  *   dx = (((float)G*sg - mg) - xhat*mgx) / sigma,  xhat = ((float)q*s - mu)/sigma
  * Outputs dx (fp32) if != NULL and/or gq = Q(dx, qo) (int8, the next Conv2d_q grad
- * quantiser) with sharded per-channel sums of gq into gcolsum [LBT_NSHARD][2C].           */
+ * quantiser, at most 8 bits) with sharded per-channel sums of gq into gcolsum [LBT_NSHARD][2C]. */
 typedef struct lbt_chain_bwd_b {
   const int8_t* G; lbt_qdesc qng; const int8_t* qn_codes; lbt_qdesc qn; const float* ms;
   const int64_t* sums; int64_t n;

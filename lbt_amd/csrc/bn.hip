@@ -818,6 +818,7 @@ extern "C" int lbt_bn_chain_bwd_a(const lbt_chain_bwd_a* a, void* stream) {
 
 extern "C" int lbt_bn_chain_bwd_b(const lbt_chain_bwd_b* a, void* stream) {
   if (!shape_ok(a->rows, a->inner, a->C)) return LBT_EINVAL;
+  if (a->gq && a->qo.bits > 8) return LBT_EINVAL;  // int8 gq codes; the int32 channel sums of q^2 assume |q| <= 2^7
   dim3 grid;
   int rpt;
   if (!grid_for(a->rows, a->inner, grid, rpt)) return LBT_EINVAL;
@@ -836,6 +837,7 @@ extern "C" int lbt_bn_chain_bwd_b(const lbt_chain_bwd_b* a, void* stream) {
 extern "C" int lbt_bn_chain_bwd_b_pair(const lbt_chain_bwd_b* a, const lbt_chain_bwd_b* b, void* stream) {
   if (!a || !b || !shape_ok(a->rows, a->inner, a->C)) return LBT_EINVAL;
   if (a->rows != b->rows || a->inner != b->inner || a->C != b->C) return LBT_EINVAL;
+  if ((a->gq && a->qo.bits > 8) || (b->gq && b->qo.bits > 8)) return LBT_EINVAL;  // as lbt_bn_chain_bwd_b
   const int f = bwd_b_flags(*a);
   if (f != bwd_b_flags(*b)) return LBT_EINVAL;
   dim3 grid;

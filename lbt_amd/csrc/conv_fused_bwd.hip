@@ -422,6 +422,7 @@ extern "C" int lbt_conv_bwd_fused_i8(const lbt_conv_bwd* q, void* stream) {
   }
   if (q->ksd != 4 * ((9 * CS + 3) / 4) || !q->wd) return LBT_EINVAL;
   if (q->w4 && q->qw.bits > 4) return LBT_EINVAL;
+  if (q->b.qo.bits > 8) return LBT_EINVAL;  // int8 gq codes; the int32 channel sums of q^2 assume |q| <= 2^7
   WgradArgs wa{};
   uint32_t wblocks = 0;
   int wcs = 0;
@@ -929,6 +930,7 @@ extern "C" int lbt_conv_bwd2_fused_i8(const lbt_conv_bwd2* q, void* stream) {
   }
   if (q->ksd1 != 4 * ((9 * 2 * CS + 3) / 4) || q->ksds != 4 || !q->wd1 || !q->wds) return LBT_EINVAL;
   if (q->w4 && (q->qw1.bits > 4 || q->qws.bits > 4)) return LBT_EINVAL;
+  if (q->b1.qo.bits > 8 || q->bs.qo.bits > 8) return LBT_EINVAL;  // int8 gq codes; int32 channel sums of q^2
   ConvBwd2Args p;
   p.b1 = q->b1; p.bs = q->bs; p.wd1 = q->wd1; p.wds = q->wds; p.qw1 = q->qw1; p.qws = q->qws; p.H = d1.H; p.a = a;
   const int64_t tiles = (int64_t)d1.N * (d1.H / tile_rows(CS));

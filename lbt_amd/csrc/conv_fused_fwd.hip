@@ -63,6 +63,7 @@ extern "C" int lbt_conv_fwd_fused_i8(const lbt_conv_fwd* q, void* stream) {
   if (!q->yq || !noise_ok(q->qout) || !q->wcolsum || !q->wf) return LBT_EINVAL;
   if (q->ksf != 4 * ((9 * CS + 3) / 4)) return LBT_EINVAL;
   if (q->w4 && q->qw.bits > 4) return LBT_EINVAL;
+  if (q->qout.bits > 8) return LBT_EINVAL;  // int8 codes; the int32 channel sums of q^2 assume |q| <= 2^7
   ConvFwdArgs p;
   p.c = a; p.wf = q->wf; p.wcolsum = q->wcolsum; p.qw = q->qw; p.H = d.H;
   p.yq = q->yq; p.qout = q->qout; p.ychsum = q->ychsum;
@@ -131,6 +132,7 @@ extern "C" int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* q, void* stream) {
     return LBT_EINVAL;
   if (q->ksf1 != 4 * ((9 * CS + 3) / 4) || q->ksfs != 4) return LBT_EINVAL;
   if (q->w4 && (q->qw1.bits > 4 || q->qws.bits > 4)) return LBT_EINVAL;
+  if (q->qout1.bits > 8 || q->qouts.bits > 8) return LBT_EINVAL;  // int8 codes; int32 channel sums of q^2
   ConvFwd2Args p;
   p.c = a; p.wf1 = q->wf1; p.wfs = q->wfs; p.wcolsum1 = q->wcolsum1; p.wcolsums = q->wcolsums;
   p.qw1 = q->qw1; p.qws = q->qws; p.H = d1.H; p.yq1 = q->yq1; p.yqs = q->yqs; p.qout1 = q->qout1;

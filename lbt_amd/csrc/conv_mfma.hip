@@ -393,6 +393,7 @@ int fwd_setup(const int8_t* xq, int32_t x_u8off, const int8_t* wf, int32_t ksf, 
   p.colsum = x_u8off ? wcolsum : nullptr;
   if (x_u8off && !wcolsum) return LBT_EINVAL;
   if (yq && qout.stochastic && !qout.noise) return LBT_EINVAL;  // quantising epilogue reads the noise table
+  if (yq && qout.bits > 8) return LBT_EINVAL;  // int8 codes; the int32 channel sums of q^2 assume |q| <= 2^7
   p.d = d; p.qa = qx; p.qb = qw; p.y = y; p.add_src = nullptr; p.yq = yq; p.qout = qout; p.ychsum = ychsum;
   p.M = (int64_t)d.N * d.Ho * d.Wo; p.ncol = d.Cout;
   return 0;

@@ -16,7 +16,19 @@ namespace {
 
 constexpr int kThreads = 256;
 
+// 64-bit wave_chan_reduce (the squares of 9..16-bit codes)
+LBT_DEV long long wave_chan_reduce64(long long v, int period) {
+  if (period)
+    for (int o = period; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // rows x inner, inner % 4 == 0: vectorised path.
+// Channel sums: a lane's partials cover at most 64 rows (rpt) and a wave reduction adds at most 64
+// lanes. WIDE = false (codes of <= 8 bits, |q| <= 2^7): 64 rows * 2^14 * 64 lanes = 2^26 < 2^31, so S1
+// and S2 stay in int32 on the lane-swap reductions. WIDE = true (9..16-bit codes, q^2 <= 2^30): the
+// squares are accumulated and reduced in 64 bits (S1: 64 * 2^15 * 64 = 2^27 still fits int32).
+template <bool WIDE>
 __global__ __launch_bounds__(kThreads) void quantize_rows_kernel(
     const float* __restrict__ x, void* __restrict__ out, int out_kind, int64_t rows, int64_t inner,
     int rpt, lbt_qdesc q, int64_t* __restrict__ chsum, int C) {
@@ -31,7 +43,9 @@ __global__ __launch_bounds__(kThreads) void quantize_rows_kernel(
     __syncthreads();
   }
   int ov1 = 0, ov2 = 0;
-  int s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  using Sq = std::conditional_t<WIDE, long long, int>;
+  int s1[4] = {0, 0, 0, 0};
+  Sq s2[4] = {0, 0, 0, 0};
   if (g < groups) {
     Noise4 n = {{0.f, 0.f, 0.f, 0.f}};
     if (q.stochastic) n = qnoise4(q, s.step, g);
@@ -64,13 +78,23 @@ __global__ __launch_bounds__(kThreads) void quantize_rows_kernel(
         *reinterpret_cast<float4*>((float*)out + base) = o;
       }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { s1[k] += c[k]; s2[k] += c[k] * c[k]; }
+      for (int k = 0; k < 4; ++k) { s1[k] += c[k]; s2[k] += (Sq)(c[k] * c[k]); }
     }
   }
   if (chsum) {
     const int per = chan_period(C);
     const int ch = (int)((g << 2) % C);
-    if (chan_scatter_ok(per)) {  // uniform: row lane >> 4 ends with channel ch + (lane >> 4)
+    if constexpr (WIDE) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { s1[k] = wave_chan_reduce(s1[k], per); s2[k] = wave_chan_reduce64(s2[k], per); }
+      if (chan_owner(per)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (s1[k]) atomicAdd((unsigned long long*)&sh_sum[ch + k], (unsigned long long)(long long)s1[k]);
+          if (s2[k]) atomicAdd((unsigned long long*)&sh_sum[C + ch + k], (unsigned long long)s2[k]);
+        }
+      }
+    } else if (chan_scatter_ok(per)) {  // uniform: row lane >> 4 ends with channel ch + (lane >> 4)
       const int cr = ch + (int)((threadIdx.x & 63) >> 4);
       const int v1 = chan_scatter4(s1, per), v2 = chan_scatter4(s2, per);
       if (chan_scatter_owner(per)) {
@@ -234,6 +258,7 @@ extern "C" int lbt_dfxp_quantize(const float* x, void* out, int out_kind, int64_
   if (q.bits < 1 || q.bits > 31 || (q.bits > 16 && out_kind != LBT_OUT_F32)) return LBT_EINVAL;
   if ((out_kind == LBT_OUT_I8 && q.bits > 8) || (out_kind == LBT_OUT_U8OFF && q.bits > 9)) return LBT_EINVAL;
   if (chsum && (C <= 0 || inner % C)) return LBT_EINVAL;
+  if (chsum && q.bits > 16) return LBT_EINVAL;  // channel sums are defined for integer codes (<= 16 bits) only
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = rows * inner;
   const bool vec = (inner % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
@@ -248,8 +273,12 @@ extern "C" int lbt_dfxp_quantize(const float* x, void* out, int out_kind, int64_
     const int64_t yblocks = (rows + rpt - 1) / rpt;
     if (yblocks > 65535) return LBT_EINVAL;
     const size_t shm = chsum ? sizeof(long long) * 2 * C : 0;
-    hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)gblocks, (unsigned)yblocks), dim3(kThreads), shm, st,
-                       x, out, out_kind, rows, inner, (int)rpt, q, chsum, C);
+    if (q.bits > 8)
+      hipLaunchKernelGGL(quantize_rows_kernel<true>, dim3((unsigned)gblocks, (unsigned)yblocks), dim3(kThreads), shm,
+                         st, x, out, out_kind, rows, inner, (int)rpt, q, chsum, C);
+    else
+      hipLaunchKernelGGL(quantize_rows_kernel<false>, dim3((unsigned)gblocks, (unsigned)yblocks), dim3(kThreads), shm,
+                         st, x, out, out_kind, rows, inner, (int)rpt, q, chsum, C);
   } else {
     int64_t blocks = (n + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
