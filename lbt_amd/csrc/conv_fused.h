@@ -106,61 +106,47 @@ LBT_DEV void halo_pad_fill(int8_t* img, int row0, int H, int word) {
   }
 }
 
-// ---- reductions on DPP / permlane swaps only (no LDS). row_total_dpp: every lane of a 16-lane row ends
-// with the row's total.
-LBT_DEV int row_total_dpp(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);  // row_ror:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false);  // row_ror:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  return v;
-}
-// the whole wave's total in every lane: the rows, then the row pairs and the halves (dfxp_device.h)
-LBT_DEV int wave_total(int v) { return half_pair_sum(row_pair_sum(row_total_dpp(v))); }
-
-// ---- per-lane overflow counts, on the VALU only: the quantisers' asymmetric predicate x >= T or
+// ---- overflow counts as wave totals on the scalar unit: the quantisers' asymmetric predicate x >= T or
 // x < -T (T a power of two) is max(x, -x*(1-2^-24)) >= T -- for x < 0 the product rounds to >= T
 // exactly when -x > T (the float after T, T(1+2^-23), gives T(1+2^-24-2^-47), which rounds down to T;
 // -x = T gives T(1-2^-24), representable and < T). A NaN threshold (lanes that must not count: halo
-// pixels, which the owning workgroup counts) compares false. Two compares + two carry-adds per element
-// and no lane masks live in SGPRs (the __ballot form kept one 64-bit mask per predicate live across the
-// unrolled elements and spilled them into VGPR lanes); ov_wave / ov_stage4 turn the lane counts into
-// wave totals once per kernel.
-LBT_DEV void ov_count2(pf2 xm, float T1, float T2, int& c1, int& c2) {
+// pixels, which the owning workgroup counts) compares false. Each compare leaves its 64-bit lane mask in
+// an SGPR pair; a scalar population count and a scalar add fold it into the running total of its
+// quantiser, c = c1 | c2 << 16 (a wave counts < 2^16 elements per quantiser: one SGPR per quantiser),
+// so c holds wave totals (the same in every lane): one VALU instruction per compare, no per-lane
+// counter registers and no wave reduction at the kernel end. The empty asm pins the total per element
+// pair: without it the compiler sinks the population counts to the totals' use at the kernel end and
+// keeps every element's mask live (v_writelane spills of SGPR pairs). Callers run it in wave-uniform
+// control flow only, with loop exits and selects the compiler can see are scalar (v_readfirstlane of the
+// wave index): a total merged at a divergent branch would be copied into a VGPR.
+LBT_DEV int mask_count(bool p) { return __builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
+// max(a, b) as the bare instruction: fmaxf first canonicalises (v_max x, x, x) every operand the compiler
+// cannot prove canonical. The result differs from fmaxf only in which NaN comes out, and it is only compared.
+LBT_DEV float max_raw(float a, float b) {
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+LBT_DEV void ov_count2(pf2 xm, float T1, float T2, int& c) {
   const pf2 n = xm * pk(-0x1.fffffep-1f, -0x1.fffffep-1f);
-  const float a0 = fmaxf(xm.x, n.x), a1 = fmaxf(xm.y, n.y);
-  c1 += (a0 >= T1) + (a1 >= T1);
-  c2 += (a0 >= T2) + (a1 >= T2);
+  const float a0 = max_raw(xm.x, n.x), a1 = max_raw(xm.y, n.y);
+  c += mask_count(a0 >= T1) + mask_count(a1 >= T1) + ((mask_count(a0 >= T2) + mask_count(a1 >= T2)) << 16);
+  asm volatile("" : "+s"(c));
 }
 // the same for xm >= 0 (inputs after a ReLU): x < -T cannot hold
-LBT_DEV void ov_count2_pos(pf2 xm, float T1, float T2, int& c1, int& c2) {
-  c1 += (xm.x >= T1) + (xm.y >= T1);
-  c2 += (xm.x >= T2) + (xm.y >= T2);
+LBT_DEV void ov_count2_pos(pf2 xm, float T1, float T2, int& c) {
+  c += mask_count(xm.x >= T1) + mask_count(xm.y >= T1) + ((mask_count(xm.x >= T2) + mask_count(xm.y >= T2)) << 16);
+  asm volatile("" : "+s"(c));
 }
-// Keep the counts of a phase computed inside it: otherwise the compiler sinks the compares to
-// the counts' use at the kernel end and keeps every element's operand live across the phases.
-LBT_DEV void pin_counts(int& c1, int& c2) { asm volatile("" : "+v"(c1), "+v"(c2)); }
+// A wave's packed totals of quantiser i of nq into counts_stage_w's slots (lane 0 stores)
+LBT_DEV void ov_stage_w(int i, int nq, int c, int* sh) {
+  counts_stage_w(i, nq, c & 0xffff, (int)((unsigned)c >> 16), sh);
+}
 LBT_DEV float ov_thr(bool cnt, float T) { return cnt ? T : __builtin_nanf(""); }
-// lane counts (each < 2^16) -> the wave totals, in every lane
-LBT_DEV void ov_wave(int& c1, int& c2) {
-  const int t = wave_total(c1 | (c2 << 16));
-  c1 = t & 0xffff;
-  c2 = t >> 16;
-}
-// Four quantisers' packed lane counts (c1 | c2 << 16 each, as ov_wave) -> their wave totals,
-// staged at counts_stage_w's slots i0 .. i0 + 3 (slots >= nq skipped): one rows_scatter4 leaves
-// quantiser r's four-row sums in row r, the DPP steps finish the row (10 VALU exchanges where four
-// ov_wave calls spend 24).
-LBT_DEV int ov_pack(int c1, int c2) { return c1 | (c2 << 16); }
-LBT_DEV void ov_stage4(int i0, int nq, int v0, int v1, int v2, int v3, int* sh) {
-  const int t = row_total_dpp(rows_scatter4(v0, v1, v2, v3));
-  const int lane = (int)(threadIdx.x & 63), i = i0 + (lane >> 4);
-  if ((lane & 15) == 0 && i < nq) {
-    int* p = sh + (int)(threadIdx.x >> 6) * 2 * nq + 2 * i;
-    p[0] = t & 0xffff;
-    p[1] = t >> 16;
-  }
-}
+// the same from a mask that is 0 where the lanes count and kOvNan where they must not: T > 0 with every
+// exponent bit set is a NaN. One mask serves all thresholds of an element (one register, not one each).
+constexpr int kOvNan = 0x7fc00000;
+LBT_DEV float ov_thr(int nanmask, float T) { return __int_as_float(__float_as_int(T) | nanmask); }
 
 // ---- the element chains run on pk2.h's packed fp32 pairs: the fused conv kernels are VALU-bound (SQ:
 // VALU busy ~70 % of the kernel), so every multiply / add / fma of a channel quad is two packed ops;

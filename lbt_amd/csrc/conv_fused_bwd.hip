@@ -166,17 +166,23 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   }
 
   // ---------------- phase 1: pass B over the rows + halo -> LDS gq image
-  int ovq1 = 0, ovq2 = 0;
+  // the wave index as a scalar: the wave-uniform loop exits and halo tests below are then scalar branches
+  // and selects, so the overflow totals (ov_count2) never pass through a VGPR
+  const int wu = __builtin_amdgcn_readfirstlane(wave);
+  int ovq = 0;
   int s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
-    if (it * kBThreads + wave * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
+    if (it * kBThreads + wu * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
     const int g = tid + it * kBThreads;
     const int ry = g / (W * C4), x = g / C4 - ry * W;
     const int y = ylo + ry, hy = y - row0 + 1;
     const int pix = hy * Wp + x + 1;  // the pixel's cell of the LDS halo image
     const bool own = hy >= 1 && hy <= TH;
-    const float T1 = ov_thr(own, so.L), T2 = ov_thr(own, so.Lh);
+    // a wave's 64 groups lie in one row (W * C4 == 128): its own-ness from the wave's first group, a scalar
+    const int hyw = ylo + (it * kBThreads + wu * 64) / (W * C4) - row0 + 1;
+    const int nanw = hyw >= 1 && hyw <= TH ? 0 : kOvNan;
+    const float T1 = ov_thr(nanw, so.L), T2 = ov_thr(nanw, so.Lh);
     int G[4], q[4], c[4];
     unpack4_i8(Gv[it], G);
     unpack4_i8(Qv[it], q);
@@ -191,7 +197,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       const pf2 t2 = xh * rmgx2[h];
       const pf2 dx = pdiv_nz(t1 - t2, sg2[h], rsc2[h]);
       const pf2 xm = dx * so.m;
-      ov_count2(xm, T1, T2, ovq1, ovq2);
+      ov_count2(xm, T1, T2, ovq);
       const pf2 fl = qfloor2(so, xm, u[h]);
       c[2 * h] = (int)fl.x;
       c[2 * h + 1] = (int)fl.y;
@@ -206,7 +212,6 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       }
     }
   }
-  pin_counts(ovq1, ovq2);
   halo_pad_fill<C, TH>(sh.gq, row0, H, 0);  // outside the image: the conv's zero padding
   WI::store(sh.w, wimg);
   __syncthreads();
@@ -261,7 +266,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   LBT_TSB(3);
 
   // ---------------- phase 3: pass A over the tile (conv_bwd2_kernel's phase 3 is a copy of this one)
-  int ov[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+  int ov[2][2] = {{0, 0}, {0, 0}};  // [branch][qrg | qng]
   int acc3[NB][4][4];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   }
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    if (NQ % kBThreads && tid + j * kBThreads >= NQ) break;  // uniform per wave
+    if (NQ % kBThreads && wu * 64 + j * kBThreads >= NQ) break;  // uniform per wave (NQ % 64 == 0)
     const int pix = (tid + j * kBThreads) / C4;
     const uint32_t off = (uint32_t)(row0 * W * C + pix * C + cq);
     const float4 t = *reinterpret_cast<const float4*>(sh.tile + pix * (C + 4) + cq);
@@ -316,12 +321,12 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const pf2 xm = g[h] * qrg[b].m;
-        ov_count2(xm, qrg[b].L, qrg[b].Lh, ov[b][0][0], ov[b][0][1]);
+        ov_count2(xm, qrg[b].L, qrg[b].Lh, ov[b][0]);
         const pf2 f1 = qfloor2(qrg[b], xm, ur[h]);  // G2 codes
         const pf2 gh = f1 * qrg[b].inv_m;
         const pf2 d = gh * gam2a[b][h];
         const pf2 dm = d * qng[b].m;
-        ov_count2(dm, qng[b].L, qng[b].Lh, ov[b][1][0], ov[b][1][1]);
+        ov_count2(dm, qng[b].L, qng[b].Lh, ov[b][1]);
         const pf2 f2c = qfloor2(qng[b], dm, un[h]);  // Gc codes
         const int G2[2] = {(int)f1.x, (int)f1.y};
         Gc[2 * h] = (int)f2c.x;
@@ -360,11 +365,11 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
     }
   }
   // slots [qo | qrg, qng of branch 1 | qrg, qng of branch 2] (counts_publish sums the kBNW waves)
-  ov_stage4(0, 5, ov_pack(ovq1, ovq2), ov_pack(ov[0][0][0], ov[0][0][1]), ov_pack(ov[0][1][0], ov[0][1][1]),
-            NB == 2 ? ov_pack(ov[1][0][0], ov[1][0][1]) : 0, sh.cnt);
-  if constexpr (NB == 2) {
-    ov_wave(ov[1][1][0], ov[1][1][1]);
-    counts_stage_w(4, 5, ov[1][1][0], ov[1][1][1], sh.cnt);
+  ov_stage_w(0, 5, ovq, sh.cnt);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    ov_stage_w(1 + 2 * b, 5, ov[b][0], sh.cnt);
+    ov_stage_w(2 + 2 * b, 5, ov[b][1], sh.cnt);
   }
   __syncthreads();
   LBT_TSB(4);
@@ -631,7 +636,8 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
   LBT_TS(1);
 
   // ---------------- phase 1: both pass-B chains -> LDS gradient-code images
-  int ov1a = 0, ov2a = 0, ov1b = 0, ov2b = 0;
+  int ova = 0, ovb = 0;
+  const int g0w = __builtin_amdgcn_readfirstlane(tid) & ~63;  // the wave's first thread
   int s1a[4] = {0, 0, 0, 0}, s2a[4] = {0, 0, 0, 0}, s1b[4] = {0, 0, 0, 0}, s2b[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int it = 0; it < kIt; ++it) {
@@ -661,7 +667,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
     unpack4_i8(Gv[it], G);
     unpack4_i8(Qv[it], q);
     const pf2 u[2] = {pk(Uv[it].x, Uv[it].y), pk(Uv[it].z, Uv[it].w)};
-    int o1 = 0, o2 = 0;
+    int o = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const pf2 x1 = pcvt(q[2 * h], q[2 * h + 1]) * sn.inv_m;
@@ -672,15 +678,17 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
       const pf2 t2 = xh * mx2[h];
       const pf2 dx = pdiv_nz(t1 - t2, sg2[h], rc2[h]);
       const pf2 xm = dx * so.m;
-      ov_count2(xm, T1, T2, o1, o2);
+      ov_count2(xm, T1, T2, o);
       const pf2 fl = qfloor2(so, xm, u[h]);
       c[2 * h] = in ? (int)fl.x : 0;  // outside the image: the conv's zero padding
       c[2 * h + 1] = in ? (int)fl.y : 0;
     }
     const int w = pack4_i8(c);
+    // r1 from the wave's first group: a scalar, so the wave totals stay on the scalar unit
+    const bool r1w = it * kBThreads + g0w < NG1;
+    ova += r1w ? o : 0;
+    ovb += r1w ? 0 : o;
     if (r1) {
-      ov1a += o1;
-      ov2a += o2;
       *reinterpret_cast<int*>(sh.g1 + pix * Cq + cqq) = w;
       if (own) {
         st_out(p.b1.gq + imgq + (uint32_t)((y * Wq + x) * Cq + cqq), w);
@@ -691,8 +699,6 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
         }
       }
     } else {
-      ov1b += o1;
-      ov2b += o2;
       if (valid) *reinterpret_cast<int*>(sh.gs + pix * Cq + cqq) = w;
       if (own) {
         st_out(p.bs.gq + imgq + (uint32_t)((y * Wq + x) * Cq + cqq), w);
@@ -704,8 +710,6 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
       }
     }
   }
-  pin_counts(ov1a, ov2a);
-  pin_counts(ov1b, ov2b);
   __syncthreads();
   LBT_TS(2);
 
@@ -763,7 +767,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
   LBT_TS(3);
 
   // ---------------- phase 3: pass A over the tile (conv_bwd_kernel's phase 3)
-  int ov[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+  int ov[2][2] = {{0, 0}, {0, 0}};  // [branch][qrg | qng]
   int acc3[NB][4][4];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
@@ -812,12 +816,12 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const pf2 xm = g[h] * qrg[b].m;
-        ov_count2(xm, qrg[b].L, qrg[b].Lh, ov[b][0][0], ov[b][0][1]);
+        ov_count2(xm, qrg[b].L, qrg[b].Lh, ov[b][0]);
         const pf2 f1 = qfloor2(qrg[b], xm, ur[h]);  // G2 codes
         const pf2 gh = f1 * qrg[b].inv_m;
         const pf2 d = gh * gam2a[b][h];
         const pf2 dm = d * qng[b].m;
-        ov_count2(dm, qng[b].L, qng[b].Lh, ov[b][1][0], ov[b][1][1]);
+        ov_count2(dm, qng[b].L, qng[b].Lh, ov[b][1]);
         const pf2 f2c = qfloor2(qng[b], dm, un[h]);  // Gc codes
         const int G2[2] = {(int)f1.x, (int)f1.y};
         Gc[2 * h] = (int)f2c.x;
@@ -858,13 +862,12 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_bwd2_kernel(C
     }
   }
   constexpr int NQ = 2 + 2 * NB;  // [qo1 | qos | qrg, qng of branch 1 | of branch 2]
-  ov_stage4(0, NQ, ov_pack(ov1a, ov2a), ov_pack(ov1b, ov2b), ov_pack(ov[0][0][0], ov[0][0][1]),
-            ov_pack(ov[0][1][0], ov[0][1][1]), sh.cnt);
-  if constexpr (NB == 2) {
-    ov_wave(ov[1][0][0], ov[1][0][1]);
-    counts_stage_w(4, NQ, ov[1][0][0], ov[1][0][1], sh.cnt);
-    ov_wave(ov[1][1][0], ov[1][1][1]);
-    counts_stage_w(5, NQ, ov[1][1][0], ov[1][1][1], sh.cnt);
+  ov_stage_w(0, NQ, ova, sh.cnt);
+  ov_stage_w(1, NQ, ovb, sh.cnt);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    ov_stage_w(2 + 2 * b, NQ, ov[b][0], sh.cnt);
+    ov_stage_w(3 + 2 * b, NQ, ov[b][1], sh.cnt);
   }
   __syncthreads();
   LBT_TS(4);

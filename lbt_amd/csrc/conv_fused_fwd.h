@@ -44,8 +44,13 @@ struct FwdShared {
   int cnt[INF ? 1 : kBNW * 2 * 4];             // counters: R (2 branches), X, output (INF: unused)
 };
 
+// waves per SIMD asked of the register allocator: the two-branch 2-row W4 tile of 32 channels keeps the 6
+// it has always had (80 VGPRs: three workgroups per CU) -- at 4 the scalar overflow counters leave it 82
+__host__ __device__ constexpr int fwd_waves(int CS, int NB, bool W4, int TH, bool INF) {
+  return (CS == 4 && TH >= 4) ? 2 : (CS == 2 && NB == 2 && W4 && TH == 2 && !INF) ? 6 : 4;
+}
 template <int CS, int NB, int F, bool W4, int TH = tile_rows(CS), bool INF = false>
-__global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_fwd_fused_kernel(ConvFwdArgs p) {
+__global__ __launch_bounds__(kBThreads, fwd_waves(CS, NB, W4, TH, INF)) void conv_fwd_fused_kernel(ConvFwdArgs p) {
   using T = FusedTile<CS, TH>;
   constexpr int C = T::C, C4 = T::C4, NT = T::NT, W = T::W, Wp = T::Wp, kMaxKS = T::kMaxKS;
   constexpr int kBIt = T::kBIt, NQ = T::NQ, J = T::J, NPR = T::NPR;
@@ -192,23 +197,30 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
     }
 
   // ---------------- phase 1: the chain over the rows + halo -> LDS input codes
-  int ovr[2][2] = {{0, 0}, {0, 0}}, ovx1 = 0, ovx2 = 0;
+  // the wave index as a scalar where counters are compiled: the wave-uniform loop exits and halo tests are
+  // then scalar branches and selects, and the overflow totals (ov_count2) never pass through a VGPR
+  int wu = wave;
+  if constexpr (!INF) wu = __builtin_amdgcn_readfirstlane(wave);
+  int ovr[2] = {0, 0}, ovx = 0;
 #pragma unroll
   for (int it = 0; it < kBIt; ++it) {
-    if (it * kBThreads + wave * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
+    if (it * kBThreads + wu * 64 >= ngrp) break;  // uniform per wave (ngrp % 64 == 0: every lane has a group)
     const int g = tid + it * kBThreads;
     const int ry = g / (W * C4), x = g / C4 - ry * W;
     const int y = ylo + ry, hy = y - row0 + 1;
     const int pix = hy * Wp + x + 1;  // the pixel's cell of the LDS halo image
     const bool own = hy >= 1 && hy <= TH;
+    // a wave's 64 groups lie in one row (W * C4 == 128): its own-ness from the wave's first group, a scalar
+    const int hyw = ylo + (it * kBThreads + wu * 64) / (W * C4) - row0 + 1;
+    const int nanw = hyw >= 1 && hyw <= TH ? 0 : kOvNan;
     const uint32_t e = (uint32_t)((y * W + x) * C + cq);
     pf2 v[2];  // the channel quad as two packed pairs
     float T1[2], T2[2];
     if constexpr (!INF) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        T1[b] = ov_thr(own, qr[b].L);
-        T2[b] = ov_thr(own, qr[b].Lh);
+        T1[b] = ov_thr(nanw, qr[b].L);
+        T2[b] = ov_thr(nanw, qr[b].Lh);
       }
     }
 #pragma unroll
@@ -224,7 +236,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
         const pf2 x2 = x1 - pm2[b][h];
         const pf2 t = pdiv_nz(x2, psy2[b][h], psr2[b][h]);
         const pf2 xm = t * qr[b].m;
-        if constexpr (!INF) ov_count2(xm, T1[b], T2[b], ovr[b][0], ovr[b][1]);
+        if constexpr (!INF) ov_count2(xm, T1[b], T2[b], ovr[b]);
         fl[h] = qfloor2(qr[b], xm, u[h]);  // the R codes
         const pf2 xr = fl[h] * qr[b].inv_m;
         const pf2 m1 = xr * gam2[b][h];
@@ -241,13 +253,13 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
     for (int h = 0; h < 2; ++h) v[h] = pk(v[h].x > 0.f ? v[h].x : 0.f, v[h].y > 0.f ? v[h].y : 0.f);
     if (YST && own) st_out4(a.y, (uint32_t)(img + e), make_float4(v[0].x, v[0].y, v[1].x, v[1].y));
     const pf2 uo[2] = {pk(nov[it].x, nov[it].y), pk(nov[it].z, nov[it].w)};
-    const float X1 = ov_thr(own, so1.L), X2 = ov_thr(own, so1.Lh);
+    const float X1 = ov_thr(nanw, so1.L), X2 = ov_thr(nanw, so1.Lh);
     int co[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       // v >= 0 after the ReLU (NaN -> 0): the lower clip and x < -L cannot hold, the codes are >= 0
       const pf2 xm = v[h] * so1.m;
-      if constexpr (!INF) ov_count2_pos(xm, X1, X2, ovx1, ovx2);
+      if constexpr (!INF) ov_count2_pos(xm, X1, X2, ovx);
       const pf2 w = xm + uo[h];
       co[2 * h] = floor_i(fminf(w.x, so1.Lm1));
       co[2 * h + 1] = floor_i(fminf(w.y, so1.Lm1));
@@ -256,11 +268,6 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
     const int cw = pack4_i8(co) ^ (int)0x80808080;
     *reinterpret_cast<int*>(sh.x + pix * C + cq) = cw;
     if (own && (!INF || a.o1)) st_out((int8_t*)a.o1 + img + e, cw);
-  }
-  if constexpr (!INF) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) pin_counts(ovr[b][0], ovr[b][1]);
-    pin_counts(ovx1, ovx2);
   }
   halo_pad_fill<C, TH>(sh.x, row0, H, (int)0x80808080);  // outside the image: the offset code of 0
   WI::store(sh.w, wimg);
@@ -301,11 +308,11 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
   LBT_TS(3);
 
   // ---------------- phase 3: the next BN's input quantiser + its channel sums
-  int ovq1 = 0, ovq2 = 0;
+  int ovq = 0;
   int s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    if (NQ % kBThreads && tid + j * kBThreads >= NQ) break;  // uniform per wave
+    if (NQ % kBThreads && (INF ? tid : wu * 64) + j * kBThreads >= NQ) break;  // uniform per wave (NQ % 64 == 0)
     const int pix3 = (tid + j * kBThreads) / C4;
     const float4 t = *reinterpret_cast<const float4*>(sh.tile + pix3 * (C + 4) + cq);
     const pf2 tv[2] = {pk(t.x, t.y), pk(t.z, t.w)};
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const pf2 xm = tv[h] * sq.m;
-      if constexpr (!INF) ov_count2(xm, sq.L, sq.Lh, ovq1, ovq2);
+      if constexpr (!INF) ov_count2(xm, sq.L, sq.Lh, ovq);
       fl[h] = qfloor2(sq, xm, u[h]);
     }
     const int c[4] = {(int)fl[0].x, (int)fl[0].y, (int)fl[1].x, (int)fl[1].y};
@@ -336,8 +343,10 @@ __global__ __launch_bounds__(kBThreads, (CS == 4 && TH >= 4) ? 2 : 4) void conv_
       }
     }
     // slots [qr of branch 1 | qr of branch 2 | qo1 | qout]
-    ov_stage4(0, 4, ov_pack(ovr[0][0], ovr[0][1]), NB == 2 ? ov_pack(ovr[NB - 1][0], ovr[NB - 1][1]) : 0,
-              ov_pack(ovx1, ovx2), ov_pack(ovq1, ovq2), sh.cnt);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) ov_stage_w(b, 4, ovr[b], sh.cnt);
+    ov_stage_w(2, 4, ovx, sh.cnt);
+    ov_stage_w(3, 4, ovq, sh.cnt);
     __syncthreads();
     LBT_TS(4);
 #pragma unroll
@@ -517,7 +526,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
   }
 
   // ---------------- phase 1: the chain over the input rows -> the two LDS code images
-  int ovr1 = 0, ovr2 = 0, ovx1 = 0, ovx2 = 0, ovs1 = 0, ovs2 = 0;
+  int ovr = 0, ovx = 0, ovs = 0;
 #pragma unroll
   for (int it = 0; it < kIt; ++it) {
     if (it * kBThreads >= NG) break;  // uniform
@@ -539,7 +548,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
       const pf2 x2 = x1 - pm2[h];
       const pf2 t = pdiv_nz(x2, psy2[h], psr2[h]);
       const pf2 xm = t * qr.m;
-      if constexpr (!INF) ov_count2(xm, T1, T2, ovr1, ovr2);
+      if constexpr (!INF) ov_count2(xm, T1, T2, ovr);
       fl[h] = qfloor2(qr, xm, u[h]);  // the R codes
       const pf2 xr = fl[h] * qr.inv_m;
       const pf2 m1 = xr * gam2[h];
@@ -560,12 +569,12 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
     for (int h = 0; h < 2; ++h) {
       // v >= 0 after the ReLU: only the upper clip can act, the codes are >= 0
       const pf2 xm = v[h] * so1.m;
-      if constexpr (!INF) ov_count2_pos(xm, X1, X2, ovx1, ovx2);
+      if constexpr (!INF) ov_count2_pos(xm, X1, X2, ovx);
       const pf2 w1 = xm + u1[h];
       c1[2 * h] = floor_i(fminf(w1.x, so1.Lm1));
       c1[2 * h + 1] = floor_i(fminf(w1.y, so1.Lm1));
       const pf2 zm = v[h] * so2.m;
-      if constexpr (!INF) ov_count2_pos(zm, Z1, Z2, ovs1, ovs2);
+      if constexpr (!INF) ov_count2_pos(zm, Z1, Z2, ovs);
       const pf2 w2 = zm + u2[h];
       c2[2 * h] = floor_i(fminf(w2.x, so2.Lm1));
       c2[2 * h + 1] = floor_i(fminf(w2.y, so2.Lm1));
@@ -582,11 +591,6 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
       st_out((int8_t*)a.o1 + img + e, cw1);
       st_out((int8_t*)a.o2 + img + e, cw2);
     }
-  }
-  if constexpr (!INF) {
-    pin_counts(ovr1, ovr2);
-    pin_counts(ovx1, ovx2);
-    pin_counts(ovs1, ovs2);
   }
   __syncthreads();
   LBT_TS(2);
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
   LBT_TS(3);
 
   // ---------------- phase 3: both BNs' input quantisers + channel sums
-  int ovq[2][2] = {{0, 0}, {0, 0}};
+  int ovq[2] = {0, 0};
   int s1[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, s2[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   {
     const int pix3 = tid / Cq4;
@@ -643,7 +647,7 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const pf2 xm = tv[h] * sq.m;
-        if constexpr (!INF) ov_count2(xm, sq.L, sq.Lh, ovq[b][0], ovq[b][1]);
+        if constexpr (!INF) ov_count2(xm, sq.L, sq.Lh, ovq[b]);
         fl[h] = qfloor2(sq, xm, u[h]);
       }
       const int c[4] = {(int)fl[0].x, (int)fl[0].y, (int)fl[1].x, (int)fl[1].y};
@@ -670,10 +674,11 @@ __global__ __launch_bounds__(kBThreads, CS == 1 ? 4 : 2) void conv_fwd2_kernel(C
       }
     }
     // slots [qr | qo1 | qo2 | qout1 | qouts]
-    ov_stage4(0, 5, ov_pack(ovr1, ovr2), ov_pack(ovx1, ovx2), ov_pack(ovs1, ovs2), ov_pack(ovq[0][0], ovq[0][1]),
-              sh.cnt);
-    ov_wave(ovq[1][0], ovq[1][1]);
-    counts_stage_w(4, 5, ovq[1][0], ovq[1][1], sh.cnt);
+    ov_stage_w(0, 5, ovr, sh.cnt);
+    ov_stage_w(1, 5, ovx, sh.cnt);
+    ov_stage_w(2, 5, ovs, sh.cnt);
+    ov_stage_w(3, 5, ovq[0], sh.cnt);
+    ov_stage_w(4, 5, ovq[1], sh.cnt);
     __syncthreads();
     LBT_TS(4);
     counts_publish_nw<kBNW>(0, 5, a.b1.qr, sh.cnt);
