@@ -10,7 +10,7 @@ _bwd_a, _bwd_b, lbt_bn_bwd_a_wide, _masked, lbt_bn_bwd_b_wide_q); C the integer-
 (lbt_conv_fwd_i8, lbt_conv_stem_fwd, lbt_conv_fwd_igemm_q on its three kernels, lbt_conv_dgrad_chain_i8,
 lbt_conv_dgrad_igemm_bna); D the fused 3x3 kernels (lbt_conv_fwd_fused_i8, lbt_conv_bwd_fused_i8)
 and the stage transitions lbt_conv_fwd2_fused_i8, lbt_conv_bwd2_fused_i8 (no add_src: grids and saturation
-only, see _run_bwd2_fused). head.hip's quantisers are not covered.
+only, see _run_bwd2_fused). head.hip's quantisers: tests/test_head.py.
 """
 import ctypes
 

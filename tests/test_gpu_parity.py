@@ -866,7 +866,10 @@ def test_head_kernel_equals_launch_sequence(N, HW, C, K, table):
     """lbt_head_fwd_bwd + lbt_step_reduce's head block == avgpool_fwd, quantize, dense fwd,
     softmax_xent, quantize, dense wgrad + reduce, dense dgrad, avgpool_bwd as separate launches:
     every output and counter bit for bit (with noise tables and with inline Philox; N > 256
-    exercises the loss-term striding)."""
+    exercises the loss-term striding). These four shapes take one path of the kernel (no pass A, no end
+    chain, one pooling chunk, C a power of two) on data far from any decision point; tests/test_head.py
+    runs every path, the quantisers' decision points, head_reduce's pad mask and the rejections against
+    the numpy head of tests/head_oracle.py."""
     import ctypes
     from lbt_amd import _lib
     rng = np.random.default_rng(N + C)
