@@ -910,6 +910,26 @@ int lbt_pre_dense(float* grad, int32_t rows, int32_t cols, int32_t state_rows, i
  * (sample, "AUG!", counter; seed): flip = r0 & 1, oy = r1 % (2pad+1), ox = r2 % (2pad+1).    */
 int lbt_augment_flip_crop(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t pad,
                           uint64_t seed, uint64_t counter, void* stream);
+/* The batch the step reads, from a dataset held on the device (load_data main.py:65-75, the epoch
+ * loop's gather trainer.py:98-99 and preprocess_image trainer.py:24-28 in one launch). Output sample b
+ * takes source sample s = idx ? idx[b] : first + b of data [n_data][H][W][C]:
+ *   y[b] = labels[s]
+ *   v    = (float)(((double)u8 - mean[p]) * (1.0 / 128))  src_kind 0: uint8 data, mean [H*W*C] float64
+ *        = the stored float                               src_kind 1: float32 data, mean unused
+ *   X[b] = lbt_augment_flip_crop of v with the draw of sample base + b: Philox of (base + b, "AUG!",
+ *          counter; seed), flip_b = flip ? r0 & 1 : 0, oy = r1 % (2pad+1), ox = r2 % (2pad+1); the
+ *          padding is 0.0 in the normalised domain.
+ * base = 0, flip = 1 equals lbt_augment_flip_crop of the gathered, normalised batch bit for bit; pad =
+ * 0, flip = 0 is a plain gather. base as in lbt_dropout_*_at: a rank holding rows [base, base + B) of a
+ * global batch draws those rows' crops. LBT_EINVAL before any HIP call: a NULL data / labels / X / y, NULL
+ * mean with src_kind 0, src_kind outside {0, 1}, B / H / W / C / n_data <= 0, pad < 0 or >= 32768, base
+ * < 0 or base + B > 2^32, idx == NULL with first < 0 or first + B > n_data, H*W*C >= 2^31. The values
+ * in idx (device memory) are the caller's to keep inside [0, n_data); one outside reads nothing and gives
+ * a zero image with label -1. 16-byte stores when (W*C) % 4 == 0 and X is 16-byte aligned, 4-byte
+ * stores otherwise: the same values. (Added under ABI 24.)                                          */
+int lbt_batch_gather(const void* data, int32_t src_kind, const double* mean, const int32_t* labels, int64_t n_data,
+                     const int32_t* idx, int64_t first, float* X, int32_t* y, int32_t B, int32_t H, int32_t W,
+                     int32_t C, int32_t pad, int32_t flip, int64_t base, uint64_t seed, uint64_t counter, void* stream);
 
 /* Diagnostics: counts (atomically into *bad) the i < n where the BN kernels' division by a
  * reused divisor (div_by(x, recip(y)), dfxp_device.h) differs in any bit from x / y; if qa
@@ -1012,8 +1032,8 @@ int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* p, void* stream);
 
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
- * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at and lbt_bias_grad_x are additions under the
- * same number: every earlier signature and result stands.                                        */
+ * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x and lbt_batch_gather are
+ * additions under the same number: every earlier signature and result stands.                    */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kT) void pre_dense_kernel(float* __restrict__ grad,
 // flip = r.x & 1, oy = r.y % (2 pad + 1), ox = r.z % (2 pad + 1). Then
 // y[n,i,j,c] = flipped[n, i + oy - pad, j + ox - pad, c] (0 outside), flipped[.,.,j] = x[.,.,W-1-j]:
 // tf.image.random_flip_left_right -> pad_to_bounding_box(pad, pad, H+2pad, W+2pad) -> random_crop(H, W).
-constexpr uint32_t kAugStream = 0x41554721u;  // "AUG!"
+// (kAugStream: dfxp_device.h, shared with batch_input.hip.)
 
 __global__ __launch_bounds__(kT) void augment_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H,
                                                      int W, int C, int pad, uint64_t seed, uint64_t counter) {

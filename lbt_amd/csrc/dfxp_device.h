@@ -130,6 +130,11 @@ LBT_DEV U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k
 
 LBT_DEV float u24(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }  // * 2^-24
 
+// preprocess_image's draw (aux.hip, batch_input.hip): one Philox call per sample n of a batch,
+// counter (n, kAugStream, counter_lo, counter_hi), key = seed: flip = r.x & 1, oy = r.y % (2 pad + 1),
+// ox = r.z % (2 pad + 1).
+constexpr uint32_t kAugStream = 0x41554721u;  // "AUG!"
+
 // Noise for the 4 consecutive noise indices 4*blk .. 4*blk+3 of one quantiser at one step.
 struct Noise4 { float u[4]; };
 LBT_DEV Noise4 noise4(uint64_t blk, uint32_t qid, uint64_t step, uint64_t seed) {

@@ -682,6 +682,40 @@ def augment_flip_crop(x, pad, seed, counter, out=None):
     return out
 
 
+def batch_gather(data, mean, labels, out_X, out_y, idx=None, first=0, pad=0, flip=False, base=0, seed=0, counter=0):
+    """The batch the step reads from a device-resident dataset (lbt_batch_gather): sample b of out_X /
+    out_y is source sample idx[b] (or first + b) of data [n, H, W, C] -- uint8 normalised as load_data does
+    with the float64 mean [H, W, C], or float32 as is -- then preprocess_image with the draw of sample
+    base + b. idx's values are the caller's to keep inside [0, n) (lbt_amd.data.DeviceDataset checks)."""
+    if data.dtype == torch.uint8:
+        _check(data, torch.uint8, "data")
+        _check(mean, torch.float64, "mean")
+        if mean.numel() != data[0].numel():
+            raise ValueError("mean must hold one value per image element")
+        kind = 0
+    else:
+        _check(data, torch.float32, "data")
+        if mean is not None:
+            raise ValueError("float32 data is stored normalised: mean must be None")
+        kind = 1
+    _check(labels, torch.int32, "labels")
+    _check(out_X, torch.float32, "out_X")
+    _check(out_y, torch.int32, "out_y")
+    n, H, W, C = data.shape
+    B = out_X.shape[0]
+    if labels.numel() != n or out_y.numel() != B or tuple(out_X.shape[1:]) != (H, W, C):
+        raise ValueError("batch_gather: labels / out_X / out_y do not match data %s at batch %d"
+                         % (tuple(data.shape), B))
+    if idx is not None:
+        _check(idx, torch.int32, "idx")
+        if idx.numel() != B:
+            raise ValueError("idx must hold one source index per output sample")
+    call("lbt_batch_gather", ptr(data), kind, ptr(mean), ptr(labels), n, ptr(idx), int(first), ptr(out_X), ptr(out_y),
+         B, H, W, C, int(pad), int(bool(flip)), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
+    return out_X, out_y
+
+
 def maxpool_fwd(x, y, amax, d):
     _check(x, torch.float32, "x")
     with _Timed("maxpool_fwd_kernel", 4 * x.numel() + 5 * y.numel()):

@@ -33,6 +33,7 @@ import torch.distributed as dist
 
 from . import _lib
 from . import distributed as D
+from .data import DeviceDataset
 from .dfxp import ops
 
 
@@ -138,6 +139,8 @@ class Trainer:
         self._plans = {}
         self._active = model
         self._aug = None
+        self._inbuf = {}  # (batch size, sample shape) -> the (X, y) pair a DeviceDataset's batches are gathered into
+        self._perm = None  # the epoch's permutation on the device (int32)
         if logger is not None:
             logger.info("Model info:\n" + model.info())
 
@@ -416,7 +419,11 @@ class Trainer:
         """Epoch loop of trainer.py:117-192 over an in-memory dataset ((Xtr, ytr), (Xte, yte)):
         shuffled batches, preprocess_image on device (random flip + pad-4 random crop,
         lbt_augment_flip_crop), the lr schedule of :122-140, and the test loop after every epoch.
-        Returns the per-epoch test accuracies."""
+        Returns the per-epoch test accuracies.
+        A dataset (DeviceDataset, DeviceDataset | None) (lbt_amd.data) runs the same epochs from device
+        memory: see _train_device."""
+        if isinstance(self.dataset[0], DeviceDataset):
+            return self._train_device(augment)
         (Xtr, ytr), (Xte, yte) = self.dataset
         dev = self.ctx.device
         history = []
@@ -446,6 +453,106 @@ class Trainer:
                 if self.logger is not None:
                     self.logger.info("Epoch %d test accuracy %f" % (epoch + 1, acc))
         return history
+
+    # -- the same loops from a device-resident dataset (lbt_amd/data.py) ----------------------
+    def _batch_buffers(self, ds, n):
+        """The fixed (X, y) pair every batch of n samples is gathered into: a model that binds its inputs
+        then holds one captured graph per batch size."""
+        key = (n,) + tuple(ds.shape[1:])
+        if key not in self._inbuf:
+            dev = self.ctx.device
+            self._inbuf[key] = (torch.empty(key, dtype=torch.float32, device=dev),
+                                torch.empty(n, dtype=torch.int32, device=dev))
+        return self._inbuf[key]
+
+    def _train_device(self, augment):
+        """train() over (DeviceDataset, DeviceDataset | None): the epoch's permutation is drawn on the host
+        as in train() (the same torch seed gives the same order) and uploaded once; each step is one
+        lbt_batch_gather launch -- gather, load_data's normalisation, preprocess_image with the draws
+        lbt_augment_flip_crop makes at this step -- into the batch size's buffer pair, then the step, on
+        one stream. No batch crosses PCIe and nothing synchronises inside the epoch (but the logger line
+        every 100 batches). The gather is launched ahead of the step's graph, not captured into it: its
+        arguments change every step. Bit for bit the host loop on ds.host_float()."""
+        ds, ds_te = self.dataset
+        n = len(ds)
+        history = []
+        for epoch in range(self.n_epoch):
+            if epoch == 0:
+                self.get_train_op()
+            elif epoch in (80, 120, 140):
+                self.lr *= self.lr_decay_factor
+                self.get_train_op()
+            perm = torch.randperm(n)
+            if self._perm is None or self._perm.numel() != n:
+                self._perm = torch.empty(n, dtype=torch.int32, device=self.ctx.device)
+            ds.upload_index(perm, out=self._perm)
+            self.batch_sizes = []
+            for b in range(0, n, self.batch_size):  # the final partial batch too (trainer.py:98)
+                nb = min(self.batch_size, n - b)
+                X, y = self._batch_buffers(ds, nb)
+                ds.batch(X, y, idx=self._perm[b:b + nb], pad=4 if augment else 0, flip=bool(augment),
+                         seed=self.ctx.seed, counter=self.global_step, check=False)
+                loss = self.step(X, y)
+                self.batch_sizes.append(nb)
+                if self.logger is not None and (b // self.batch_size + 1) % 100 == 0:
+                    self.logger.info("Batch %d loss %f" % (b // self.batch_size + 1, loss.item()))
+            if ds_te is not None and len(ds_te):
+                acc, _ = self.evaluate(ds_te)
+                history.append(acc)
+                if self.logger is not None:
+                    self.logger.info("Epoch %d test accuracy %f" % (epoch + 1, acc))
+        return history
+
+    def _evaluate_device(self, ds, batch_size, testing):
+        """evaluate() / evaluate(testing=True) over a DeviceDataset: the batches are first = b slices gathered
+        on the device; each batch's accuracy and loss stay device tensors until one copy at the end, and
+        are summed on the host in the order and type of the host loops (fp32 values added in double), so the
+        returned pair and every side effect equal theirs."""
+        from .fused import FusedResNet
+        m = self.model
+        fused = isinstance(m, FusedResNet)
+        restore = not (testing and fused)  # inference plans touch neither the counters nor the element counts
+        if restore:
+            saved, saved_nelem = self.ctx.counts.clone(), self.ctx.nelem.clone()
+        if testing and not fused:
+            was_training = getattr(m, "training", True)
+            m.set_testing()
+        accs, losses, shared = [], [], not fused
+        try:
+            for b in range(0, len(ds), batch_size):
+                nb = min(batch_size, len(ds) - b)
+                Xb, yb = self._batch_buffers(ds, nb)
+                ds.batch(Xb, yb, first=b)
+                if not testing:
+                    p, shared = self._eval_model(nb)
+                elif fused:
+                    key = ("testing", nb)
+                    if key not in self._eval:
+                        self._eval[key] = FusedResNet(m.model, inference=True)
+                    p = self._eval[key]
+                else:
+                    p = m
+                logits = p.forward(Xb)
+                loss = p.compute_loss(yb)
+                accs.append((logits.argmax(dim=1).to(torch.int32) == yb).float().mean())
+                losses.append(loss.detach().reshape(-1)[0].clone())  # the plan rewrites its loss buffer
+        finally:
+            if testing and not fused and was_training:
+                m.set_training()
+            if restore:
+                self.ctx.counts.copy_(saved)
+                self.ctx.nelem.copy_(saved_nelem)
+                for q in self.ctx.quantizers:  # (as evaluate: the cached counts describe the test batches)
+                    q._nelem = None
+                if shared:
+                    self._graphs = None
+        if not accs:
+            return 0.0, 0.0
+        acc_sum = loss_sum = 0.0
+        for a, l in zip(torch.stack(accs).cpu().tolist(), torch.stack(losses).cpu().tolist()):
+            acc_sum += a
+            loss_sum += l
+        return acc_sum / len(accs), loss_sum / len(accs)
 
     # -- test loop and checkpoint (trainer.py:164-197) ----------------------------------------
     def _eval_model(self, n):
@@ -503,7 +610,7 @@ class Trainer:
                 self._graphs = None
         return acc_sum / max(nb, 1), loss_sum / max(nb, 1)
 
-    def evaluate(self, X, y, batch_size=1000, testing=False):
+    def evaluate(self, X, y=None, batch_size=1000, testing=False):
         """The reference's test loop (trainer.py:166-190): per batch of 1000 the forward pass in
         training mode (batch-statistic BN, stochastic quantisers, and Dropout_q still dropping, at the
         current step's mask -- the reference never runs set_testing, :164-165), loss and accuracy;
@@ -512,7 +619,13 @@ class Trainer:
         testing=True: the same loop and return value in testing mode instead (running-average BN, Dropout_q
         the identity; what a trained network is deployed as): nothing is updated. A FusedResNet runs it on
         forward-only inference plans (FusedResNet(model, inference=True)), a layer-wise model between
-        set_testing() and set_training()."""
+        set_testing() and set_training().
+        evaluate(ds) with a DeviceDataset (no y): the same loops on batches gathered on the device, the same
+        return value and side effects (_evaluate_device)."""
+        if isinstance(X, DeviceDataset):
+            if y is not None:
+                raise TypeError("a DeviceDataset carries its labels: evaluate(ds, batch_size=..., testing=...)")
+            return self._evaluate_device(X, batch_size, testing)
         if testing:
             return self._evaluate_testing(X, y, batch_size)
         dev = self.ctx.device
