@@ -1030,10 +1030,58 @@ typedef struct lbt_conv_fwd2 {
 } lbt_conv_fwd2;
 int lbt_conv_fwd2_fused_i8(const lbt_conv_fwd2* p, void* stream);
 
+/* ---------------------------------------------------------------- training summaries ---------
+ * The reference's per-layer tf.summary.scalars (W_range / X_range / grad_range / b_range / g_range,
+ * W_mean / b_mean / g_mean; dynamic_fixed_point.py:180-190, 275-285, 372-382, 578-582, 667-675) and the
+ * loss / accuracy it fetches with them (trainer.py:148-155), recorded on the device INSIDE a captured
+ * step: lbt_summary_record after the backward and BEFORE the update (the update zeroes the overflow
+ * counters that drove its range decisions), lbt_summary_commit after it. Both write ring slot
+ * cursor[0] % capacity; commit advances cursor[0] (device memory: a replayed graph needs no argument
+ * change). Every source is only read -- the counters are NOT zeroed.
+ *
+ * One record, lbt_summary_record_bytes(nslots, nparams) = 32 + 16 * nslots + 8 * nparams bytes:
+ *   offset  0  uint64  step      step[0] at record time (steps completed before this one)
+ *           8  int32   batch
+ *          12  int32   correct   #samples b whose LOWEST-index maximum of logits[b][0..classes) equals
+ *                                labels[b] (a NaN never compares greater)
+ *          16  float   loss      loss[0] at COMMIT time (a fused plan's loss is final after its tail)
+ *          20  int32   nslots
+ *          24  int32   nparams
+ *          28  int32   0
+ *          32                 int32  exps[nslots]   the ranges this step's quantisers used
+ *          32 +  4 * nslots   int32  c1[nslots]     sum over the LBT_NSHARD shards of counts[slot][.][0]
+ *          32 +  8 * nslots   int32  c2[nslots]     ... of counts[slot][.][1]
+ *          32 + 12 * nslots   float  nelem[nslots]
+ *          32 + 16 * nslots   double sum[nparams]   sum of the fp32 elements w[seg_off[p] .. seg_off[p+1])
+ * Parameter sums: a segment is cut into chunks of LBT_SUMMARY_CHUNK elements, one workgroup each (16-byte
+ * loads between a scalar head and tail: segment starts are not 16-byte aligned); a chunk's double partial
+ * goes to scratch[p * cps + chunk], cps = ceil(max_seg / LBT_SUMMARY_CHUNK) (at least 1), and commit adds a
+ * segment's partials in chunk order. Fixed association, no floating-point atomics: the same data gives
+ * the same bits. Elements of a segment longer than max_seg are not summed (nothing is read out of range).
+ * lbt_summary_scratch_bytes(nparams, max_seg) = 8 * nparams * cps (both queries: -LBT_EINVAL for a negative argument).
+ * LBT_EINVAL before any HIP call: s == NULL, capacity <= 0, nslots < 0, nparams < 0, batch < 0, classes <
+ * 1, a NULL ring / cursor / step, NULL exps / counts / nelem with nslots > 0, NULL w / seg_off / scratch
+ * or max_seg <= 0 with nparams > 0, NULL logits / labels with batch > 0, a grid past 2^31 - 1 workgroups;
+ * commit also a NULL loss. The ring holds capacity records; the caller keeps record + commit paired.  */
+#define LBT_SUMMARY_CHUNK 16384
+typedef struct lbt_summary {
+  /* sources */
+  const int32_t* exps; const int32_t* counts; const float* nelem; int32_t nslots;
+  int32_t nparams; const float* w; const int64_t* seg_off; /* device int64 [nparams + 1] */ int64_t max_seg;
+  const float* logits; const int32_t* labels; int32_t batch, classes;
+  const float* loss; const uint64_t* step;
+  /* sink */
+  void* ring; int64_t capacity; uint64_t* cursor; double* scratch;
+} lbt_summary;
+int64_t lbt_summary_record_bytes(int32_t nslots, int32_t nparams);
+int64_t lbt_summary_scratch_bytes(int32_t nparams, int64_t max_seg);
+int lbt_summary_record(const lbt_summary* s, void* stream);
+int lbt_summary_commit(const lbt_summary* s, void* stream);
+
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
- * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x and lbt_batch_gather are
- * additions under the same number: every earlier signature and result stands.                    */
+ * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather and
+ * lbt_summary_* are additions under the same number: every earlier signature and result stands.   */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

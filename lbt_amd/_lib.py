@@ -189,6 +189,17 @@ class FSeg(ctypes.Structure):
     _fields_ = [("off", c_int64), ("n", c_int64), ("kind", c_int32), ("qx", QDesc), ("qg", QDesc), ("wd2", c_float)]
 
 
+class Summary(ctypes.Structure):
+    """lbt_summary: what one recording step reads (sources) and where its record goes (sink)."""
+    _fields_ = [("exps", c_void_p), ("counts", c_void_p), ("nelem", c_void_p), ("nslots", c_int32),
+                ("nparams", c_int32), ("w", c_void_p), ("seg_off", c_void_p), ("max_seg", c_int64),
+                ("logits", c_void_p), ("labels", c_void_p), ("batch", c_int32), ("classes", c_int32),
+                ("loss", c_void_p), ("step", c_void_p),
+                ("ring", c_void_p), ("capacity", c_int64), ("cursor", c_void_p), ("scratch", c_void_p)]
+
+
+SUMMARY_CHUNK = 16384  # LBT_SUMMARY_CHUNK
+
 _P = c_void_p
 _SIGS = {
     "lbt_abi_version": [],
@@ -327,6 +338,10 @@ _SIGS = {
     "lbt_batch_gather": [_P, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                          c_int32, c_int64, c_uint64, c_uint64, _P],
     "lbt_step_update": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_int32, _P, _P],
+    "lbt_summary_record_bytes": [c_int32, c_int32],
+    "lbt_summary_scratch_bytes": [c_int32, c_int64],
+    "lbt_summary_record": [ctypes.POINTER(Summary), _P],
+    "lbt_summary_commit": [ctypes.POINTER(Summary), _P],
 }
 EXPORTED = sorted(_SIGS)
 
@@ -349,7 +364,8 @@ def load(path=LIB_PATH):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int32
-    lib.lbt_igemm_workspace_bytes.restype = c_int64  # the one int64-valued query
+    for name in ("lbt_igemm_workspace_bytes", "lbt_summary_record_bytes", "lbt_summary_scratch_bytes"):
+        getattr(lib, name).restype = c_int64  # the int64-valued queries
     if lib.lbt_abi_version() != ABI_VERSION:
         raise ImportError("lbt_amd ABI mismatch: library %d, bindings %d" % (lib.lbt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -280,18 +280,40 @@ class FusedResNet:
         """The step's last launch: the reductions (+ the optimiser and the range update)."""
         return self._tail_upd if update and self.updates_in_step() else self._tail_fused
 
-    def train_fwd_bwd(self, X, labels, update=False):
+    def _summary_launches(self, s):
+        """The two launches that record this step into s (a lbt_summary whose sink and shared sources the
+        Trainer set): this plan's logits, loss, labels and batch are written into s here, the launches are
+        built once per descriptor."""
+        s.logits, s.loss, s.labels = self.logits.data_ptr(), self.loss.data_ptr(), self._head.labels
+        s.batch, s.classes = int(self.logits.shape[0]), int(self.logits.shape[1])
+        if getattr(self, "_sum", None) is None or self._sum[0] is not s:
+            L = self._launcher(_lib.load())
+            w = sum(p.numel() for p in self._flat_params())
+            self._sum = (s, L("lbt_summary_record", ctypes.byref(s), k="summary_record_kernel",
+                              nb=4 * w + 4 * self.logits.numel() + 8 * ops.NSHARD * s.nslots),
+                         L("lbt_summary_commit", ctypes.byref(s), k="summary_commit_kernel", nb=8 * s.nparams))
+        return self._sum[1], self._sum[2]
+
+    def step_launches(self, update=False, summary=None):
+        """The launches train_fwd_bwd runs, in order. summary (a lbt_summary): the record launch between the
+        backward and the tail -- the tail's update zeroes the counters it reads -- and the commit after it."""
+        tail = self.step_tail(update)
+        if summary is None:
+            return self._fwd + self._hfused + self._bwd + tail
+        rec, com = self._summary_launches(summary)
+        return self._fwd + self._hfused + self._bwd + [rec] + tail + [com]
+
+    def train_fwd_bwd(self, X, labels, update=False, summary=None):
         """forward + compute_loss + backward of one training step, the head as one launch
         (lbt_head_fwd_bwd): same results bit for bit as the three calls. update=True (and
         updates_in_step()): the last launch also applies SGD-momentum and update_range (the Trainer's
-        optimiser step, bit-identical). Returns whether it did."""
+        optimiser step, bit-identical). Returns whether it did. summary: see step_launches."""
         self._training_only("train_fwd_bwd()")
         self._ensure(X)
         self._bind(X, labels)
-        tail = self.step_tail(update)
-        for f in self._fwd + self._hfused + self._bwd + tail:
+        for f in self.step_launches(update, summary):
             f()
-        return tail is not self._tail_fused
+        return self.step_tail(update) is not self._tail_fused
 
     # ------------------------------------------------------------------ streams
     def _on_side(self, run, force=False):

@@ -24,6 +24,11 @@ MI355X-native execution:
   - ``DfxpContext(world_size=N, rank=r)``: the plain models with ``Dropout_q`` train data-parallel on
     the exact int64 exchange (bias numerators included), each rank drawing its shard's bits of the
     global batch's dropout mask: N ranks on the shards equal one process on the whole batch.
+* the reference's training summaries (``trainer.py:148-155``: every layer's ``tf.summary.scalar``s with loss
+  and accuracy, every 100th batch) are recorded on the device: ``Trainer(summary_every=K)`` replays, on every
+  K-th step, a second captured graph of the step with ``lbt_summary_record`` between the backward and the
+  update -- which zeroes the overflow counters that drove its range decisions -- and ``lbt_summary_commit``
+  after it (``lbt_amd/summary.py``). Every other step replays the graph it replays without summaries.
 """
 import os
 import sys
@@ -64,8 +69,14 @@ class FlatParams:
 class Trainer:
     def __init__(self, model, dataset=None, logger=None, logdir=None, lr=1e-2, lr_decay_factor=0.5,
                  lr_decay_epoch=50, momentum=0.95, n_epoch=5, batch_size=128, use_graph=True,
-                 process_group=None, exchange=None, capture_comm=None):
-        """exchange: run the data-parallel exchange (default: when the process group has > 1 rank;
+                 process_group=None, exchange=None, capture_comm=None, summary_every=0, summary_capacity=1024):
+        """summary_every = K > 0: the K-th, 2K-th, ... steps of this trainer (counted from 1) record the
+        reference's training summaries on the device (lbt_amd/summary.py; read them with summaries()):
+        those steps replay a second captured graph of the same step with lbt_summary_record between the
+        backward and the update and lbt_summary_commit after it; every other step replays the graph it
+        replays without summaries. summary_capacity: records the device ring holds between two reads.
+        0: off, nothing changes anywhere.
+        exchange: run the data-parallel exchange (default: when the process group has > 1 rank;
         True at world 1 exercises the same path -- an all-reduce over one rank is the identity).
         capture_comm: put the step's collectives (the exchange, SyncBN's statistics) INSIDE the
         captured HIP graph, so a step is one graph launch (default: on for the nccl = RCCL backend,
@@ -93,6 +104,13 @@ class Trainer:
             capture_comm = (dist_on and dist.get_backend(process_group) == "nccl"
                             and os.environ.get("LBT_CAPTURE_COMM", "1") == "1")
         self.capture_comm = bool(capture_comm) and dist_on
+        self.summary_every = int(summary_every)
+        if self.summary_every < 0:
+            raise ValueError("summary_every must be >= 0, got %r" % (summary_every,))
+        if self.dp and self.summary_every > 0:
+            raise NotImplementedError("summaries of a data-parallel trainer: the overflow counters are summed "
+                                      "across ranks inside the exchange, so no rank holds the step's totals "
+                                      "where lbt_summary_record reads them (summary_every must be 0)")
         # a context that declares its rank: shard-aware dropout masks and the exact exchange with biases
         ranked = self.ctx.rank is not None
         if ranked and dist_on and self.ctx.rank != dist.get_rank(process_group):
@@ -132,9 +150,17 @@ class Trainer:
         self._fused_update = hasattr(model, "set_optimizer") and not self.dp
         self._sync_optimizer()
         self.global_step = 0
+        self._gflag = {}  # recording? -> captured graphs on the static inputs (models that bind none)
         self._graphs = None
         self._static = None
-        self._gcache = {}  # (X ptr, y ptr, shape) -> captured graphs (models that bind inputs)
+        self._gcache = {}  # (X ptr, y ptr, shape, recording?) -> captured graphs (models that bind inputs)
+        # summaries: one ring / cursor for every plan, one lbt_summary per plan (its own logits, loss, labels)
+        self.logdir = logdir
+        self._sring = None
+        self._sdesc = {}
+        if self.summary_every > 0:
+            from .summary import SummaryRing
+            self._sring = SummaryRing(self.ctx, self.flat, summary_capacity)
         self._eval = {}
         self._plans = {}
         self._active = model
@@ -143,6 +169,65 @@ class Trainer:
         self._perm = None  # the epoch's permutation on the device (int32)
         if logger is not None:
             logger.info("Model info:\n" + model.info())
+
+    @property
+    def _graphs(self):
+        """The graphs of the last captured or replayed step; None forgets every graph on the static inputs."""
+        return self._glast
+
+    @_graphs.setter
+    def _graphs(self, g):
+        self._glast = g
+        if g is None:
+            self._gflag = {}
+
+    # -- summaries ---------------------------------------------------------------------------
+    def _records(self):
+        """Whether the step about to run records: the K-th, 2K-th, ... of this trainer, decided on the host."""
+        return self.summary_every > 0 and (self.global_step + 1) % self.summary_every == 0
+
+    def _summary(self, m):
+        """Plan / model m's lbt_summary (the shared sink and sources; m's own pointers are set per step)."""
+        s = self._sdesc.get(id(m))
+        if s is None:
+            s = self._sdesc[id(m)] = (m, self._sring.desc())
+        return s[1]
+
+    def _summary_call(self, name, m, y=None):
+        """lbt_summary_record / _commit of a layer-wise model around Trainer._update: its logits, loss and
+        the step's labels as they lie after the forward + backward (fixed buffers once warmed up)."""
+        s = self._summary(m)
+        if y is not None:
+            s.logits, s.loss, s.labels = m.logits.data_ptr(), m.loss.data_ptr(), y.data_ptr()
+            s.batch, s.classes = int(m.logits.shape[0]), int(m.logits.shape[1])
+        with ops._Timed(name[4:] + "_kernel", 0):
+            _lib.call(name, _lib.ctypes.byref(s), _lib.stream())
+
+    def summaries(self):
+        """The records committed since the last call, oldest first (lbt_amd.summary.decode's dicts: step,
+        batch, loss, accuracy, scalars under the reference's tags, param_sums, overflow). Synchronises and
+        copies the ring once; records overwritten before being read are counted in summary_dropped."""
+        if self._sring is None:
+            return []
+        return self._sring.drain()
+
+    @property
+    def summary_dropped(self):
+        return 0 if self._sring is None else self._sring.dropped
+
+    def _log_batch(self, batch, loss):
+        """The every-100-batches logging point of both epoch loops. With summaries: drain them, log the
+        reference's line (trainer.py:155) from the newest record, append each to logdir/train/summaries.jsonl."""
+        recs = self.summaries()
+        if recs and self.logdir:
+            from .summary import append_jsonl
+            append_jsonl(os.path.join(self.logdir, "train", "summaries.jsonl"), recs)
+        if self.logger is None:
+            return
+        if recs:
+            self.logger.info("Batch %d loss %f acc %f" % (batch, recs[-1]["loss"], recs[-1]["accuracy"]))
+        else:
+            self.logger.info("Batch %d loss %f" % (batch, loss.item()))
 
     @staticmethod
     def _has_dropout(model):
@@ -219,9 +304,10 @@ class Trainer:
             self._graphs = None
         return p
 
-    def _fwd_bwd(self, X, y, update=False):
+    def _fwd_bwd(self, X, y, update=False, summary=False):
         """The step's forward + backward; update=True lets a fused plan apply the optimiser and the range
-        update in its last launch. Returns whether it did (then _update must not run)."""
+        update in its last launch. Returns whether it did (then _update must not run). summary: a fused
+        plan records the step itself, around its tail (a layer-wise model's launches bracket _update)."""
         m = self._active = self._plan(X.shape[0])
         did = False
         nel = getattr(m, "_nelem", None)
@@ -230,7 +316,10 @@ class Trainer:
         if not getattr(m, "zeroes_own_sums", False):
             self.ctx.zero_sums()
         if hasattr(m, "train_fwd_bwd"):
-            did = bool(m.train_fwd_bwd(X, y, update=update and self._fused_update))
+            if summary:
+                did = bool(m.train_fwd_bwd(X, y, update=update and self._fused_update, summary=self._summary(m)))
+            else:  # (a step that does not record makes the call it always made)
+                did = bool(m.train_fwd_bwd(X, y, update=update and self._fused_update))
         elif self._lw_exact:
             x = self._xchg
             self._loss_n = int(X.shape[0]) * self.world
@@ -277,13 +366,22 @@ class Trainer:
         else:  # optimiser + range update in one launch
             self.ctx.update_range_op(sgd=(self.flat.w, self.flat.a, self.flat.g, self.lr, self.momentum, 1.0))
 
-    def _eager(self, X, y):
+    def _update_recorded(self, y, rec):
+        """_update, between lbt_summary_record and lbt_summary_commit when a layer-wise model's step records."""
+        lw = rec and not hasattr(self._active, "train_fwd_bwd")
+        if lw:
+            self._summary_call("lbt_summary_record", self._active, y)
+        self._update()
+        if lw:
+            self._summary_call("lbt_summary_commit", self._active)
+
+    def _eager(self, X, y, rec=False):
         self._sync_optimizer()  # an assignment to self.lr / self.momentum takes effect on the fused update too
-        did = self._fwd_bwd(X, y, update=not self.dp)
+        did = self._fwd_bwd(X, y, update=not self.dp, summary=rec)
         if self.dp:
             self._exchange()
         if not did:
-            self._update()
+            self._update_recorded(y, rec)
 
     def _warmup(self, X, y):
         """One un-captured forward + backward that allocates every per-layer buffer before a capture.
@@ -305,18 +403,22 @@ class Trainer:
             bn.X_mean_running.copy_(m)
             bn.X_var_running.copy_(v)
 
-    def _capture(self, X, y):
+    def _capture(self, X, y, rec=False):
         m = self.model
-        if hasattr(m, "input_buffer") and hasattr(m, "label_buffer"):
-            # capture on the model's own buffers: no copies inside the graph
-            self._static = (m.input_buffer(X.shape), m.label_buffer(y.shape[0]))
-        else:
-            self._static = (torch.empty_like(X), torch.empty_like(y))
+        fresh = not self._gflag or self._static is None or self._static[0].shape != X.shape
+        if fresh:
+            self._graphs = None  # another shape re-sizes the per-layer buffers: every graph on them goes
+            if hasattr(m, "input_buffer") and hasattr(m, "label_buffer"):
+                # capture on the model's own buffers: no copies inside the graph
+                self._static = (m.input_buffer(X.shape), m.label_buffer(y.shape[0]))
+            else:
+                self._static = (torch.empty_like(X), torch.empty_like(y))
         sX, sy = self._static
         sX.copy_(X)
         sy.copy_(y)
-        self._warmup(sX, sy)
-        self._graphs = self._capture_step(sX, sy)
+        if fresh:  # (the other flag's graph of this shape left every buffer allocated)
+            self._warmup(sX, sy)
+        self._gflag[rec] = self._graphs = self._capture_step(sX, sy, rec)
 
     def _comm_capturable(self):
         """Capture the exchange ALONE into a throwaway graph (never replayed) once: whether this RCCL /
@@ -338,7 +440,7 @@ class Trainer:
             torch.cuda.synchronize()
         return self._comm_probe
 
-    def _capture_step(self, X, y):
+    def _capture_step(self, X, y, rec=False):
         """(g1, g2): the step as one graph (no exchange, or captured collectives), else the forward +
         backward and the update as two graphs with the host-issued exchange between them. When the
         exchange cannot be captured (``_comm_capturable``) it runs from the host, loudly (not for SyncBN
@@ -346,20 +448,20 @@ class Trainer:
         if self.dp and self.capture_comm and not getattr(self.model, "sync_bn", False):
             if not self._comm_capturable():
                 self.capture_comm = False
-        return self._capture_step_once(X, y)
+        return self._capture_step_once(X, y, rec)
 
-    def _capture_step_once(self, X, y):
+    def _capture_step_once(self, X, y, rec=False):
         one = not self.dp or self.capture_comm
         # thread-local capture: the process group's watchdog thread queries events meanwhile
         mode = "thread_local" if self.capture_comm else "global"
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, capture_error_mode=mode):
-            did = self._fwd_bwd(X, y, update=not self.dp)
+            did = self._fwd_bwd(X, y, update=not self.dp, summary=rec)
             if one:
                 if self.dp:
                     self._exchange()
                 if not did:
-                    self._update()
+                    self._update_recorded(y, rec)
         g2 = None
         if not one:
             g2 = torch.cuda.CUDAGraph()
@@ -367,12 +469,17 @@ class Trainer:
                 self._update()
         return g1, g2
 
-    def _capture_bound(self, X, y):
+    def _capture_bound(self, X, y, rec=False):
         """Capture the step reading (X, y) in place (models with binds_inputs): one graph per batch
-        buffer pair, the first capture after a warm-up that allocates every per-layer buffer."""
+        buffer pair (and per kind of step: recording or not), the first capture after a warm-up that
+        allocates every per-layer buffer."""
         if getattr(self._plan(X.shape[0]), "_shape", 0) is None or not self._gcache:
             self._warmup(X, y)  # every plan's first run allocates its buffers outside a capture
-        return self._capture_step(X, y)
+        return self._capture_step(X, y, rec)
+
+    def _bound_room(self, rec):
+        """Whether one more bound buffer pair may get a graph: at most 8 per kind of step."""
+        return sum(1 for k in self._gcache if k[3] == rec) < 8
 
     def prepare(self, X, y):
         """Build (capture) the step's graph for this batch buffer pair without running a step -- setup
@@ -381,33 +488,37 @@ class Trainer:
         self._active = self._plan(X.shape[0])
         if not self.use_graph or (getattr(self.model, "sync_bn", False) and not self.capture_comm):
             return
-        key = (X.data_ptr(), y.data_ptr(), tuple(X.shape))
-        if getattr(self.model, "binds_inputs", False):
-            if key not in self._gcache and len(self._gcache) < 8:
-                self._gcache[key] = self._capture_bound(X, y)
-        elif self._graphs is None or self._static is None or self._static[0].shape != X.shape:
-            self._capture(X, y)
+        kinds = ([False] if self.summary_every != 1 else []) + ([True] if self.summary_every > 0 else [])
+        for rec in kinds:  # both kinds of step a trainer with summaries replays
+            key = (X.data_ptr(), y.data_ptr(), tuple(X.shape), rec)
+            if getattr(self.model, "binds_inputs", False):
+                if key not in self._gcache and self._bound_room(rec):
+                    self._gcache[key] = self._capture_bound(X, y, rec)
+            elif rec not in self._gflag or self._static is None or self._static[0].shape != X.shape:
+                self._capture(X, y, rec)
 
     def step(self, X, y):
         """One training step on batch (X [B,32,32,3] fp32 NHWC, y [B] int32), device tensors.
         A SyncBN plan holds collectives inside the step: captured with them (RCCL), else eager."""
         self._active = self._plan(X.shape[0])
+        rec = self._records()
         if not self.use_graph or (getattr(self.model, "sync_bn", False) and not self.capture_comm):
-            self._eager(X, y)
+            self._eager(X, y, rec)
         else:
-            key = (X.data_ptr(), y.data_ptr(), tuple(X.shape))
-            if getattr(self.model, "binds_inputs", False) and (key in self._gcache or len(self._gcache) < 8):
+            key = (X.data_ptr(), y.data_ptr(), tuple(X.shape), rec)
+            if getattr(self.model, "binds_inputs", False) and (key in self._gcache or self._bound_room(rec)):
                 # the batch is read where it lies: a graph per buffer pair (a loader's ring of
                 # batch buffers), no copy into static inputs inside the timed step
                 if key not in self._gcache:
-                    self._gcache[key] = self._capture_bound(X, y)
-                self._graphs = self._gcache[key]
-            elif self._graphs is None or self._static is None or self._static[0].shape != X.shape:
-                self._capture(X, y)
+                    self._gcache[key] = self._capture_bound(X, y, rec)
+                self._glast = self._gcache[key]
+            elif rec not in self._gflag or self._static is None or self._static[0].shape != X.shape:
+                self._capture(X, y, rec)
             else:
                 self._static[0].copy_(X)
                 self._static[1].copy_(y)
-            g1, g2 = self._graphs
+                self._glast = self._gflag[rec]
+            g1, g2 = self._glast
             g1.replay()
             if g2 is not None:
                 self._exchange()
@@ -445,8 +556,8 @@ class Trainer:
                     X = ops.augment_flip_crop(X, 4, self.ctx.seed, self.global_step, out=self._aug)
                 loss = self.step(X, y)
                 self.batch_sizes.append(len(idx))
-                if self.logger is not None and (b // self.batch_size + 1) % 100 == 0:
-                    self.logger.info("Batch %d loss %f" % (b // self.batch_size + 1, loss.item()))
+                if (b // self.batch_size + 1) % 100 == 0 and (self.logger is not None or self._sring is not None):
+                    self._log_batch(b // self.batch_size + 1, loss)
             if Xte is not None and len(Xte):
                 acc, _ = self.evaluate(Xte, yte)
                 history.append(acc)
@@ -494,8 +605,8 @@ class Trainer:
                          seed=self.ctx.seed, counter=self.global_step, check=False)
                 loss = self.step(X, y)
                 self.batch_sizes.append(nb)
-                if self.logger is not None and (b // self.batch_size + 1) % 100 == 0:
-                    self.logger.info("Batch %d loss %f" % (b // self.batch_size + 1, loss.item()))
+                if (b // self.batch_size + 1) % 100 == 0 and (self.logger is not None or self._sring is not None):
+                    self._log_batch(b // self.batch_size + 1, loss)
             if ds_te is not None and len(ds_te):
                 acc, _ = self.evaluate(ds_te)
                 history.append(acc)
