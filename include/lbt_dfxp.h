@@ -910,6 +910,15 @@ int lbt_pre_dense(float* grad, int32_t rows, int32_t cols, int32_t state_rows, i
  * (sample, "AUG!", counter; seed): flip = r0 & 1, oy = r1 % (2pad+1), ox = r2 % (2pad+1).    */
 int lbt_augment_flip_crop(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t pad,
                           uint64_t seed, uint64_t counter, void* stream);
+/* lbt_augment_flip_crop on a window of a larger batch: sample n of x / y draws as sample base + n, Philox
+ * of (base + n, "AUG!", counter; seed) -- a rank holding rows [base, base + N) of a global batch draws
+ * those rows' flips and crops (base as in lbt_dropout_*_at and lbt_batch_gather). Rows [base, base + N)
+ * of the plain call on the whole batch equal this call on those rows bit for bit; base = 0 IS the plain
+ * call (lbt_augment_flip_crop runs this with base 0, results unchanged). LBT_EINVAL before any HIP call:
+ * the plain call's checks (N / H / W / C <= 0, pad < 0, x == y), base < 0 or base + N > 2^32 (the draw's
+ * key is 32 bits wide). (Added under ABI 24.)                                                        */
+int lbt_augment_flip_crop_at(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t pad,
+                             int64_t base, uint64_t seed, uint64_t counter, void* stream);
 /* The batch the step reads, from a dataset held on the device (load_data main.py:65-75, the epoch
  * loop's gather trainer.py:98-99 and preprocess_image trainer.py:24-28 in one launch). Output sample b
  * takes source sample s = idx ? idx[b] : first + b of data [n_data][H][W][C]:
@@ -1078,10 +1087,26 @@ int64_t lbt_summary_scratch_bytes(int32_t nparams, int64_t max_seg);
 int lbt_summary_record(const lbt_summary* s, void* stream);
 int lbt_summary_commit(const lbt_summary* s, void* stream);
 
+/* ---- The test loop's metrics as integers (eval.hip): what a test batch's rows contribute to the
+ * reference's accuracy and loss (trainer.py:166-190), in a form that sums across ranks exactly.
+ *   row[0] = #{b < B : argmax_k logits[b][k] == labels[b]}, the LOWEST index among equal maxima (the tie
+ *            rule of lbt_summary_record's correct count and of argmax)
+ *   row[1] = the ordered double sum of the rows' loss terms (logf(sum_k expf(z_k - max)) + max) - z_label
+ *            in 2^-32 fixed point: bit for bit the loss_fx lbt_softmax_xent_n writes for the same (logits,
+ *            labels), on both of its paths (classes <= 64: one thread per row; wider: one wave per row).
+ * Nothing else is written (no dz, no loss). A label outside [0, classes) is never correct and adds no
+ * loss term. One launch, one workgroup. A batch of nb rows split over ranks: the int64 sum of the ranks'
+ * rows gives accuracy = (float)row[0] / (float)nb exactly and loss = (float)(row[1] * 2^-32 / nb) (the
+ * rounding of lbt_step_finish's loss). LBT_EINVAL before any HIP call: a NULL logits / labels / row, B <=
+ * 0, classes < 1. (Added under ABI 24.)                                                               */
+int lbt_eval_tally(const float* logits, const int32_t* labels, int32_t B, int32_t classes, int64_t* row /* [2] */,
+                   void* stream);
+
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
- * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather and
- * lbt_summary_* are additions under the same number: every earlier signature and result stands.   */
+ * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather,
+ * lbt_summary_*, lbt_augment_flip_crop_at and lbt_eval_tally are additions under the same number: every
+ * earlier signature and result stands.                                                              */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

@@ -335,6 +335,8 @@ _SIGS = {
     "lbt_grad_buffer_bwd": [_P, c_int64, _P, c_int64, c_int64, QDesc, _P, _P],
     "lbt_pre_dense": [_P, c_int32, c_int32, c_int32, c_int32, QDesc, _P, _P, _P, _P],
     "lbt_augment_flip_crop": [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint64, c_uint64, _P],
+    "lbt_augment_flip_crop_at": [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_uint64, c_uint64, _P],
+    "lbt_eval_tally": [_P, _P, c_int32, c_int32, _P, _P],
     "lbt_batch_gather": [_P, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                          c_int32, c_int64, c_uint64, c_uint64, _P],
     "lbt_step_update": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_int32, _P, _P],

@@ -5,6 +5,7 @@
 //   lbt_pre_dense           Dense_q._pre_dense_func (:397-439, dormant in the reference's trainer): the
 //                           per-element small-gradient accumulator state machine
 //   lbt_augment_flip_crop   trainer.py:24-28 preprocess_image: random left-right flip, zero pad, random crop
+//   lbt_augment_flip_crop_at  the same on rows [base, base + N) of a larger batch: their draws
 //
 // All element-parallel (each element's state is its own), one thread per element / output.
 #include "dfxp_device.h"
@@ -86,10 +87,12 @@ __global__ __launch_bounds__(kT) void pre_dense_kernel(float* __restrict__ grad,
 // flip = r.x & 1, oy = r.y % (2 pad + 1), ox = r.z % (2 pad + 1). Then
 // y[n,i,j,c] = flipped[n, i + oy - pad, j + ox - pad, c] (0 outside), flipped[.,.,j] = x[.,.,W-1-j]:
 // tf.image.random_flip_left_right -> pad_to_bounding_box(pad, pad, H+2pad, W+2pad) -> random_crop(H, W).
-// (kAugStream: dfxp_device.h, shared with batch_input.hip.)
+// (kAugStream: dfxp_device.h, shared with batch_input.hip.) base: sample n draws as sample base + n of a
+// larger batch (lbt_augment_flip_crop_at: a rank's rows of a global batch); base = 0 is the plain call.
 
 __global__ __launch_bounds__(kT) void augment_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H,
-                                                     int W, int C, int pad, uint64_t seed, uint64_t counter) {
+                                                     int W, int C, int pad, int64_t base, uint64_t seed,
+                                                     uint64_t counter) {
   const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
   const int64_t total = (int64_t)N * H * W * C;
   if (e >= total) return;
@@ -99,8 +102,8 @@ __global__ __launch_bounds__(kT) void augment_kernel(const float* __restrict__ x
   m /= W;
   const int i = (int)(m % H);
   const int n = (int)(m / H);
-  const U4 r = philox((uint32_t)n, kAugStream, (uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)seed,
-                      (uint32_t)(seed >> 32));
+  const U4 r = philox((uint32_t)(base + (int64_t)n), kAugStream, (uint32_t)counter, (uint32_t)(counter >> 32),
+                      (uint32_t)seed, (uint32_t)(seed >> 32));
   const uint32_t span = 2u * (uint32_t)pad + 1u;
   const int flip = (int)(r.x & 1u), oy = (int)(r.y % span), ox = (int)(r.z % span);
   const int si = i + oy - pad, sj0 = j + ox - pad;
@@ -151,11 +154,17 @@ extern "C" int lbt_pre_dense(float* grad, int32_t rows, int32_t cols, int32_t st
   return (int)hipGetLastError();
 }
 
-extern "C" int lbt_augment_flip_crop(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t pad,
-                                     uint64_t seed, uint64_t counter, void* stream) {
+extern "C" int lbt_augment_flip_crop_at(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C,
+                                        int32_t pad, int64_t base, uint64_t seed, uint64_t counter, void* stream) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || pad < 0 || x == y) return LBT_EINVAL;
+  if (base < 0 || base > ((int64_t)1 << 32) - N) return LBT_EINVAL;  // the draw's key is 32 bits wide
   const int64_t n = (int64_t)N * H * W * C;
   hipLaunchKernelGGL(augment_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, (hipStream_t)stream, x, y, N, H,
-                     W, C, pad, seed, counter);
+                     W, C, pad, base, seed, counter);
   return (int)hipGetLastError();
+}
+
+extern "C" int lbt_augment_flip_crop(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t pad,
+                                     uint64_t seed, uint64_t counter, void* stream) {
+  return lbt_augment_flip_crop_at(x, y, N, H, W, C, pad, 0, seed, counter, stream);
 }

@@ -18,6 +18,7 @@
 // B[k = 16*(l>>4) .. +15][col l&15]; C/D: col = l&15, row = 4*(l>>4) + reg.
 #include "dfxp_device.h"
 #include "lds_tr.h"
+#include "xent_row.h"
 
 using namespace lbt;
 
@@ -220,39 +221,26 @@ __global__ __launch_bounds__(1024) void softmax_xent_wide_kernel(const float* __
           dz[(int64_t)rr * K + k] = (p - (k == y ? 1.f : 0.f)) / (float)norm;
         }
       }
-      if (lane == 0) {
-        const float lse = logf(s) + m;
-        acc += (double)(lse - zr[y]);
-      }
+      if (lane == 0) acc += (double)xent_row_term(m, s, zr[y]);
 #pragma unroll
       for (int i = 0; i < kSxReg; ++i) v[i] = vn[i];
       continue;
     }
-    float m = -INFINITY;
-    for (int k = lane; k < K; k += 64) m = fmaxf(m, zr[k]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    float s = 0.f;
-    for (int k = lane; k < K; k += 64) s = s + expf(zr[k] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+    float m, s;
+    xent_wave_stats(zr, K, lane, m, s);
     const int y = labels[rr];
     for (int k = lane; k < K; k += 64) {
       const float p = expf(zr[k] - m) / s;
       dz[(int64_t)rr * K + k] = (p - (k == y ? 1.f : 0.f)) / (float)norm;
     }
-    if (lane == 0) {
-      const float lse = logf(s) + m;
-      acc += (double)(lse - zr[y]);
-    }
+    if (lane == 0) acc += (double)xent_row_term(m, s, zr[y]);
   }
   if (lane == 0) part[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < 16; ++w) t += part[w];
+    const double t = xent_wave_sum16(part);
     loss[0] = (float)(t / (double)norm);
-    if (loss_fx) *loss_fx = (long long)llrint(t * 4294967296.0);
+    if (loss_fx) *loss_fx = xent_loss_fx(t);
   }
 }
 

@@ -3,6 +3,7 @@
 //   mean sparse softmax cross-entropy (models.py:30-32) and MomentumOptimizer (trainer.py:81-82).
 // All HBM-bound elementwise passes with 16-byte vector accesses where the shape allows.
 #include "dfxp_device.h"
+#include "xent_row.h"
 
 using namespace lbt;
 
@@ -81,27 +82,19 @@ __global__ void softmax_xent_kernel(const float* __restrict__ z, const int32_t* 
   double part = 0.0;
   for (int r = threadIdx.x; r < N; r += blockDim.x) {
     const float* zr = z + (int64_t)r * K;
-    float m = zr[0];
-    for (int k = 1; k < K; ++k) m = zr[k] > m ? zr[k] : m;
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = s + expf(zr[k] - m);
+    float m, s;
+    xent_row_stats(zr, K, m, s);
     const int y = labels[r];
     for (int k = 0; k < K; ++k) {
       const float p = expf(zr[k] - m) / s;
       dz[(int64_t)r * K + k] = (p - (k == y ? 1.f : 0.f)) / (float)norm;
     }
-    const float lse = logf(s) + m;
-    part += (double)(lse - zr[y]);
+    part += (double)xent_row_term(m, s, zr[y]);
   }
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  const double total = xent_block_sum256(part, red);  // (launched with 256 threads)
   if (threadIdx.x == 0) {
-    loss[0] = (float)(red[0] / (double)norm);
-    if (loss_fx) *loss_fx = (long long)llrint(red[0] * 4294967296.0);
+    loss[0] = (float)(total / (double)norm);
+    if (loss_fx) *loss_fx = xent_loss_fx(total);
   }
 }
 

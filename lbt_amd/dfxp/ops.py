@@ -671,15 +671,36 @@ def pre_dense(grad, qg_desc, accu, init_flag, rem_flag):
     return grad
 
 
-def augment_flip_crop(x, pad, seed, counter, out=None):
-    """preprocess_image (trainer.py:24-28) on device: random flip + zero pad + random crop."""
+def augment_flip_crop(x, pad, seed, counter, out=None, base=0):
+    """preprocess_image (trainer.py:24-28) on device: random flip + zero pad + random crop.
+    base: x holds rows [base, base + N) of a larger batch and takes those rows' draws
+    (lbt_augment_flip_crop_at: a rank's shard of a global batch); 0 is the plain call."""
     _check(x, torch.float32, "x")
     N, H, W, C = x.shape
     if out is None:
         out = torch.empty_like(x)
+    if base:
+        call("lbt_augment_flip_crop_at", ptr(x), ptr(out), N, H, W, C, int(pad), int(base),
+             int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
+        return out
     call("lbt_augment_flip_crop", ptr(x), ptr(out), N, H, W, C, int(pad), int(seed) & 0xFFFFFFFFFFFFFFFF,
          int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
     return out
+
+
+def eval_tally(logits, labels, row):
+    """A test batch's metrics as integers (lbt_eval_tally): row [2] int64 <- (correct predictions, the loss-term
+    sum in 2^-32 fixed point) of logits [B, classes] fp32 against labels [B] int32. One launch."""
+    _check(logits, torch.float32, "logits")
+    _check(labels, torch.int32, "labels")
+    _check(row, torch.int64, "row")
+    B, K = logits.shape
+    if labels.numel() != B or row.numel() != 2:
+        raise ValueError("eval_tally: labels must hold %d entries and row 2, got %d and %d"
+                         % (B, labels.numel(), row.numel()))
+    with _Timed("eval_tally_wide_kernel" if K > 64 else "eval_tally_kernel", 4 * logits.numel() + 4 * B):
+        call("lbt_eval_tally", ptr(logits), ptr(labels), int(B), int(K), ptr(row), stream())
+    return row
 
 
 def batch_gather(data, mean, labels, out_X, out_y, idx=None, first=0, pad=0, flip=False, base=0, seed=0, counter=0):

@@ -24,6 +24,13 @@ MI355X-native execution:
   - ``DfxpContext(world_size=N, rank=r)``: the plain models with ``Dropout_q`` train data-parallel on
     the exact int64 exchange (bias numerators included), each rank drawing its shard's bits of the
     global batch's dropout mask: N ranks on the shards equal one process on the whole batch.
+* data-parallel epochs: under a process group ``train()`` shards every global batch of the epoch by rows
+  (``shard_rows``; rank 0's permutation broadcast once per epoch; each row augmented with its draw of the global
+  batch, ``lbt_batch_gather``'s / ``lbt_augment_flip_crop_at``'s ``base``), and ``evaluate()`` splits each test batch
+  where that is exact -- a SyncBN-trained FusedResNet, or its inference plans -- summing ``lbt_eval_tally``'s
+  integer rows with one all-reduce (``_evaluate_sharded``); elsewhere every rank runs the whole test loop. The
+  same script on N ranks then leaves one process's parameters, exponents and BN statistics bit for bit. Not
+  timed at N > 1 on hardware.
 * the reference's training summaries (``trainer.py:148-155``: every layer's ``tf.summary.scalar``s with loss
   and accuracy, every 100th batch) are recorded on the device: ``Trainer(summary_every=K)`` replays, on every
   K-th step, a second captured graph of the step with ``lbt_summary_record`` between the backward and the
@@ -40,6 +47,54 @@ from . import _lib
 from . import distributed as D
 from .data import DeviceDataset
 from .dfxp import ops
+
+
+def shard_rows(nb, world, rank):
+    """Rows [lo, hi) of a global batch of nb rows that rank ``rank`` of ``world`` takes: ``world`` equal
+    shards in rank order, rank r rows [r * nb / world, (r + 1) * nb / world). ValueError when nb does
+    not split evenly (uneven shards are not built)."""
+    nb, world, rank = int(nb), int(world), int(rank)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d is outside a world of %d" % (rank, world))
+    if nb < 0 or nb % world:
+        raise ValueError("a batch of %d rows does not split into %d equal shards" % (nb, world))
+    s = nb // world
+    return rank * s, (rank + 1) * s
+
+
+def epoch_batch_sizes(n, batch_size):
+    """Every batch size an epoch over n samples produces: batch_size (when a full batch fits) and the
+    final partial batch n % batch_size (trainer.py:98), in that order."""
+    n, batch_size = int(n), int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1, got %d" % batch_size)
+    return ([batch_size] if n >= batch_size else []) + ([n % batch_size] if n % batch_size else [])
+
+
+def check_epoch_shards(n, batch_size, world):
+    """The up-front check of a data-parallel epoch: every batch size it will produce splits into ``world``
+    equal shards, or ValueError naming all three."""
+    bad = [nb for nb in epoch_batch_sizes(n, batch_size) if nb % int(world)]
+    if bad:
+        raise ValueError("n = %d samples at batch_size = %d give a batch of %d rows, which does not split into "
+                         "world = %d equal shards (batch_size is the GLOBAL batch; batch_size and n %% batch_size "
+                         "must both be divisible by world)" % (n, batch_size, bad[0], world))
+
+
+def decode_tally(rows, sizes):
+    """(mean accuracy, mean loss) over the test batches from their lbt_eval_tally rows summed over the ranks:
+    rows[i] = (correct predictions, loss-term sum in 2^-32 fixed point) of batch i, sizes[i] its rows.
+    Per batch the accuracy is float32(correct) / float32(nb) -- what mean() of the 0 / 1 floats gives -- and
+    the loss float32(sum * 2^-32 / nb) computed in double (lbt_step_finish's rounding); the fp32 values are
+    added in double in batch order and divided by the number of batches, as the test loops do."""
+    import numpy as np
+    if len(rows) != len(sizes):
+        raise ValueError("%d tally rows for %d batches" % (len(rows), len(sizes)))
+    acc_sum = loss_sum = 0.0
+    for (correct, loss_fx), nb in zip(rows, sizes):
+        acc_sum += float(np.float32(int(correct)) / np.float32(int(nb)))
+        loss_sum += float(np.float32(float(int(loss_fx)) * 2.0 ** -32 / float(int(nb))))
+    return acc_sum / max(len(sizes), 1), loss_sum / max(len(sizes), 1)
 
 
 class FlatParams:
@@ -76,6 +131,8 @@ class Trainer:
         backward and the update and lbt_summary_commit after it; every other step replays the graph it
         replays without summaries. summary_capacity: records the device ring holds between two reads.
         0: off, nothing changes anywhere.
+        batch_size: the reference's (trainer.py:34) -- under a process group the GLOBAL batch of train(), which
+        every rank takes an equal shard of (step() itself takes whatever shard it is handed).
         exchange: run the data-parallel exchange (default: when the process group has > 1 rank;
         True at world 1 exercises the same path -- an all-reduce over one rank is the identity).
         capture_comm: put the step's collectives (the exchange, SyncBN's statistics) INSIDE the
@@ -104,6 +161,10 @@ class Trainer:
             capture_comm = (dist_on and dist.get_backend(process_group) == "nccl"
                             and os.environ.get("LBT_CAPTURE_COMM", "1") == "1")
         self.capture_comm = bool(capture_comm) and dist_on
+        # the epoch loops under a process group of several ranks: each rank takes its shard of every global
+        # batch (train) and, where that is exact, of every test batch (evaluate)
+        self.rank = dist.get_rank(process_group) if dist_on else 0
+        self._shard = self.dp and self.world > 1
         self.summary_every = int(summary_every)
         if self.summary_every < 0:
             raise ValueError("summary_every must be >= 0, got %r" % (summary_every,))
@@ -526,16 +587,53 @@ class Trainer:
         self.global_step += 1
         return self._active.loss
 
+    # -- sharded epochs ----------------------------------------------------------------------
+    def _check_epoch(self, n):
+        """Before an epoch loop draws, allocates or launches anything: every batch size it will produce
+        splits over the ranks (check_epoch_shards). One process: nothing to check."""
+        if self._shard:
+            check_epoch_shards(n, self.batch_size, self.world)
+
+    def _shard_of(self, nb):
+        """Rows [lo, hi) of a global batch of nb rows this rank takes: all of them in one process."""
+        return shard_rows(nb, self.world, self.rank) if self._shard else (0, nb)
+
+    def _epoch_perm(self, n):
+        """The epoch's permutation (host int64): torch.randperm(n) where the single-process loop draws it;
+        under sharding rank 0's draw, broadcast over the trainer's process group (the other ranks draw
+        nothing: only rank 0's generator has to match the single process)."""
+        if not self._shard:
+            return torch.randperm(n)
+        perm = torch.randperm(n) if self.rank == 0 else torch.empty(n, dtype=torch.int64)
+        src = dist.get_global_rank(self.pg, 0) if self.pg is not None else 0
+        if dist.get_backend(self.pg) == "nccl":  # RCCL moves device tensors
+            t = perm.to(self.ctx.device)
+            dist.broadcast(t, src=src, group=self.pg)
+            return t.cpu()
+        dist.broadcast(perm, src=src, group=self.pg)
+        return perm
+
     def train(self, augment=True):
         """Epoch loop of trainer.py:117-192 over an in-memory dataset ((Xtr, ytr), (Xte, yte)):
         shuffled batches, preprocess_image on device (random flip + pad-4 random crop,
         lbt_augment_flip_crop), the lr schedule of :122-140, and the test loop after every epoch.
         Returns the per-epoch test accuracies.
         A dataset (DeviceDataset, DeviceDataset | None) (lbt_amd.data) runs the same epochs from device
-        memory: see _train_device."""
+        memory: see _train_device.
+        Under a process group of ``world`` > 1 ranks (a data-parallel trainer) the epoch is sharded:
+        ``batch_size`` stays the GLOBAL batch (trainer.py:34); rank 0 draws the epoch's permutation where
+        the single process draws it and broadcasts it (one small collective per epoch, outside any
+        capture); of every global batch of nb rows -- the final partial one too -- rank r gathers rows
+        [r * nb / world, (r + 1) * nb / world) of the permuted batch (shard_rows) and augments them with
+        THEIR draws of the global batch (lbt_augment_flip_crop_at / lbt_batch_gather's base). Both
+        batch_size and n % batch_size must be divisible by world: checked before anything is drawn,
+        allocated or launched (ValueError). With FusedResNet(sync_bn=True), or a ranked context's plain
+        model, N ranks leave the parameters, momentum, exponents and BN statistics of one process with
+        the same torch seed, bit for bit; batch_sizes records the global nb. No timing is claimed for it."""
         if isinstance(self.dataset[0], DeviceDataset):
             return self._train_device(augment)
         (Xtr, ytr), (Xte, yte) = self.dataset
+        self._check_epoch(len(Xtr))
         dev = self.ctx.device
         history = []
         for epoch in range(self.n_epoch):
@@ -544,18 +642,20 @@ class Trainer:
             elif epoch in (80, 120, 140):
                 self.lr *= self.lr_decay_factor
                 self.get_train_op()
-            perm = torch.randperm(len(Xtr))
+            perm = self._epoch_perm(len(Xtr))
             self.batch_sizes = []
             for b in range(0, len(Xtr), self.batch_size):  # the final partial batch too (trainer.py:98)
-                idx = perm[b:b + self.batch_size]
+                nb = min(self.batch_size, len(Xtr) - b)
+                lo, hi = self._shard_of(nb)  # (one process: the whole batch)
+                idx = perm[b + lo:b + hi]
                 X = torch.as_tensor(Xtr[idx.numpy()], dtype=torch.float32).to(dev).contiguous()
                 y = torch.as_tensor(ytr[idx.numpy()], dtype=torch.int32).to(dev)
                 if augment:
                     if self._aug is None or self._aug.shape != X.shape:
                         self._aug = torch.empty_like(X)
-                    X = ops.augment_flip_crop(X, 4, self.ctx.seed, self.global_step, out=self._aug)
+                    X = ops.augment_flip_crop(X, 4, self.ctx.seed, self.global_step, out=self._aug, base=lo)
                 loss = self.step(X, y)
-                self.batch_sizes.append(len(idx))
+                self.batch_sizes.append(nb)
                 if (b // self.batch_size + 1) % 100 == 0 and (self.logger is not None or self._sring is not None):
                     self._log_batch(b // self.batch_size + 1, loss)
             if Xte is not None and len(Xte):
@@ -583,9 +683,13 @@ class Trainer:
         lbt_augment_flip_crop makes at this step -- into the batch size's buffer pair, then the step, on
         one stream. No batch crosses PCIe and nothing synchronises inside the epoch (but the logger line
         every 100 batches). The gather is launched ahead of the step's graph, not captured into it: its
-        arguments change every step. Bit for bit the host loop on ds.host_float()."""
+        arguments change every step. Bit for bit the host loop on ds.host_float().
+        Sharded (see train()): every rank holds the whole dataset on its GPU and uploads the broadcast
+        permutation; rank r's launch gathers idx = perm[b + r*s : b + (r+1)*s] with base = r*s into a
+        buffer pair of the shard's size s = nb / world."""
         ds, ds_te = self.dataset
         n = len(ds)
+        self._check_epoch(n)
         history = []
         for epoch in range(self.n_epoch):
             if epoch == 0:
@@ -593,15 +697,16 @@ class Trainer:
             elif epoch in (80, 120, 140):
                 self.lr *= self.lr_decay_factor
                 self.get_train_op()
-            perm = torch.randperm(n)
+            perm = self._epoch_perm(n)
             if self._perm is None or self._perm.numel() != n:
                 self._perm = torch.empty(n, dtype=torch.int32, device=self.ctx.device)
             ds.upload_index(perm, out=self._perm)
             self.batch_sizes = []
             for b in range(0, n, self.batch_size):  # the final partial batch too (trainer.py:98)
                 nb = min(self.batch_size, n - b)
-                X, y = self._batch_buffers(ds, nb)
-                ds.batch(X, y, idx=self._perm[b:b + nb], pad=4 if augment else 0, flip=bool(augment),
+                lo, hi = self._shard_of(nb)  # (one process: the whole batch, base 0)
+                X, y = self._batch_buffers(ds, hi - lo)
+                ds.batch(X, y, idx=self._perm[b + lo:b + hi], pad=4 if augment else 0, flip=bool(augment), base=lo,
                          seed=self.ctx.seed, counter=self.global_step, check=False)
                 loss = self.step(X, y)
                 self.batch_sizes.append(nb)
@@ -679,6 +784,75 @@ class Trainer:
             return self._eval[n], False
         return m, True
 
+    def _shards_eval(self, testing):
+        """Whether evaluate() splits its test batches over the ranks: only where the rows a rank computes
+        are the single process's -- a FusedResNet's inference plans (no batch coupling), or its training-
+        mode plans when it was trained with sync_bn=True (whole-batch moments through SyncBN). Decided from
+        what every rank shares (the trainer's world, the model's kind), so all ranks take the same path."""
+        from .fused import FusedResNet
+        m = self.model
+        return bool(self._shard and isinstance(m, FusedResNet) and (testing or m.sync_bn))
+
+    def _evaluate_sharded(self, X, y, batch_size, testing):
+        """evaluate() with every test batch split by rows over the ranks (host arrays or a DeviceDataset):
+        rank r forwards rows [r * nb / world, (r + 1) * nb / world) of each batch of nb -- training mode on a
+        SyncBN eval plan per shard size (keys ("sync", s) of self._eval; its moments are the whole batch's, so
+        logits rows and the running statistics each batch leaves are the single process's), testing mode on
+        the inference plans -- and lbt_eval_tally (one launch, in place of the argmax / == / float / mean
+        kernels and the loss launch) writes the shard's correct count and fixed-point loss sum into its row of
+        one int64 tensor [nbatches, 2]. After the loop ONE all-reduce sums the rows over the ranks and one copy
+        brings them to the host (decode_tally). A batch whose size is not divisible by world runs in the
+        redundant form on every rank (whole batch, local-BN eval plan; rank 0's tally counts). The accuracy
+        equals one process's exactly; the loss is the same fixed-point sum lbt_step_finish decodes. Counters
+        and element counts are saved and restored as in the other loops."""
+        from .fused import FusedResNet
+        m, dev, ctx = self.model, self.ctx.device, self.ctx
+        ds = X if isinstance(X, DeviceDataset) else None
+        n = len(X)
+        starts = list(range(0, n, batch_size))
+        if not starts:
+            return 0.0, 0.0
+        rows = torch.zeros((len(starts), 2), dtype=torch.int64, device=dev)
+        restore = not testing  # inference plans touch neither the counters nor the element counts
+        if restore:
+            saved, saved_nelem = ctx.counts.clone(), ctx.nelem.clone()
+        sizes = []
+        try:
+            for i, b in enumerate(starts):
+                nb = min(batch_size, n - b)
+                sizes.append(nb)
+                split = nb % self.world == 0  # (nb and world: the same on every rank)
+                lo, hi = shard_rows(nb, self.world, self.rank) if split else (0, nb)
+                if ds is not None:
+                    Xb, yb = self._batch_buffers(ds, hi - lo)
+                    ds.batch(Xb, yb, first=b + lo)
+                else:
+                    Xb = torch.as_tensor(X[b + lo:b + hi], dtype=torch.float32).to(dev).contiguous()
+                    yb = torch.as_tensor(y[b + lo:b + hi], dtype=torch.int32).to(dev)
+                if testing:
+                    key = ("testing", hi - lo)
+                    if key not in self._eval:
+                        self._eval[key] = FusedResNet(m.model, inference=True)
+                    p = self._eval[key]
+                elif split:
+                    key = ("sync", hi - lo)
+                    if key not in self._eval:
+                        self._eval[key] = FusedResNet(m.model, sync_bn=True, process_group=m.pg)
+                    p = self._eval[key]
+                else:
+                    p, _ = self._eval_model(nb)
+                logits = p.forward(Xb)
+                if split or self.rank == 0:  # a redundant batch counts once in the sum over the ranks
+                    ops.eval_tally(logits, yb, rows[i])
+        finally:
+            if restore:
+                ctx.counts.copy_(saved)
+                ctx.nelem.copy_(saved_nelem)
+                for q in ctx.quantizers:  # (as evaluate: the cached counts describe the test batches)
+                    q._nelem = None
+        dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=self.pg)
+        return decode_tally(rows.cpu().tolist(), sizes)
+
     def _evaluate_testing(self, X, y, batch_size):
         """evaluate(testing=True): the test loop in testing mode (Model.set_testing, models.py:15) -- every
         BatchNorm normalises with its running averages and nothing moves. A FusedResNet runs one
@@ -732,10 +906,15 @@ class Trainer:
         forward-only inference plans (FusedResNet(model, inference=True)), a layer-wise model between
         set_testing() and set_training().
         evaluate(ds) with a DeviceDataset (no y): the same loops on batches gathered on the device, the same
-        return value and side effects (_evaluate_device)."""
+        return value and side effects (_evaluate_device).
+        Under a process group of several ranks every rank runs the whole loop and gets the same result,
+        except where a test batch can be split by rows exactly (_evaluate_sharded): the training-mode loop
+        of a FusedResNet trained with sync_bn=True, and evaluate(testing=True) of a FusedResNet."""
+        if isinstance(X, DeviceDataset) and y is not None:
+            raise TypeError("a DeviceDataset carries its labels: evaluate(ds, batch_size=..., testing=...)")
+        if self._shards_eval(testing):
+            return self._evaluate_sharded(X, y, batch_size, testing)
         if isinstance(X, DeviceDataset):
-            if y is not None:
-                raise TypeError("a DeviceDataset carries its labels: evaluate(ds, batch_size=..., testing=...)")
             return self._evaluate_device(X, batch_size, testing)
         if testing:
             return self._evaluate_testing(X, y, batch_size)
