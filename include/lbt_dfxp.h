@@ -646,6 +646,16 @@ int lbt_bn_bwd_b_wide_q(const int16_t* G, lbt_qdesc qng, const int8_t* qn, lbt_q
 int lbt_bn_param_grads(const int64_t* sums, int32_t C, lbt_qdesc qrg, lbt_qdesc qr,
                        const float* gamma, float wd2, float* dgamma, float* dbeta, void* stream);
 
+/* SyncBN of the layer-wise models (Normalization_q.sync): the totals of a sharded statistics buffer,
+ *   total[j] = sum_{k < nshard} part[k * stride + j]   for j < stride, and nothing else is written.
+ * part is [nshard][stride] int64 -- a chsum ([LBT_NSHARD][2C]) or pass-A sums ([LBT_NSHARD][4C]) buffer --
+ * and total the first stride entries of a buffer of the same layout whose other shards the caller keeps
+ * zero: after an all-reduce SUM of those stride entries over the ranks, lbt_bn_chain_fwd / lbt_bn_moments
+ * (with n * world) and the pass-B kernels read it as the statistics of the global batch, exactly.
+ * LBT_EINVAL before any HIP call: a NULL pointer, nshard <= 0, nshard > LBT_NSHARD, stride <= 0.
+ * (Added under ABI 24.)                                                                                  */
+int lbt_sums_fold(const int64_t* part, int32_t nshard, int64_t stride, int64_t* total, void* stream);
+
 /* ---------------------------------------------------------------- glue ---------------- */
 
 /* ReLU_q forward (:986, tf.maximum(0,x)) and backward (TF _MaximumGrad: g where x > 0). */

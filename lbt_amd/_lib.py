@@ -285,6 +285,7 @@ _SIGS = {
     "lbt_bn_bwd_a_wide": [_P, QDesc, _P, _P, QDesc, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P],
     "lbt_bn_bwd_b_wide": [_P, QDesc, _P, QDesc, _P, _P, c_int64, _P, c_int64, c_int32, _P],
     "lbt_bn_param_grads": [_P, c_int32, QDesc, QDesc, _P, c_float, _P, _P, _P],
+    "lbt_sums_fold": [_P, c_int32, c_int64, _P, _P],
     "lbt_relu_fwd": [_P, _P, c_int64, _P],
     "lbt_relu_bwd": [_P, _P, _P, c_int64, _P],
     "lbt_dropout_fwd": [_P, _P, c_int64, c_float, _P, c_uint64, c_uint32, c_int32, _P],

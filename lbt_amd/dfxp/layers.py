@@ -23,6 +23,7 @@ import os
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from .. import _lib
 from .._lib import NO_Q, OUT_F32, OUT_I8, OUT_I16, OUT_U8OFF, BnNorm, BwdBranch, ChainBranch, ChainBwdA, \
@@ -749,6 +750,39 @@ class Normalization_q(Layer_q):
         self.ms = torch.zeros(2 * num_features, dtype=torch.float32, device=ctx.device)
         self.fmode = float_mode(bits, grad_bits)
         self._c = _Cache()
+        self._gsums = {}
+
+    # SyncBN (lbt_amd.distributed.sync_batchnorm): (process group, world). While the layer trains, its
+    # integer statistics -- the channel sums of Xq and the pass-A sums -- are summed over the ranks before
+    # the kernel that consumes them, which then sees the global batch's sums and n * world: N shards
+    # compute the moments, the running averages and the input gradient one process computes on the whole
+    # batch (tf.nn.moments over the batch, :588), bit for bit. None: the shard's own statistics.
+    sync = None
+
+    @property
+    def synced(self):
+        return self.sync is not None and self.train
+
+    def global_n(self, n):
+        """Elements per channel behind this layer's statistics: the shard's n, times world when synced."""
+        return n * self.sync[1] if self.synced else n
+
+    def global_sums(self, key, local):
+        """The sharded statistics buffer the consumer reads: `local` itself, or, synced, the layer's own
+        buffer of the same layout with the ranks' totals in shard 0 (ops.sums_fold, then ONE all-reduce
+        of exactly those 2C / 4C int64) and zeros in every other shard. That buffer is allocated zeroed
+        once, outside the per-step sums arena: shards 1.. are never written. `local` is left as it is:
+        bn_param_grads reads it on the side stream for the dgamma / dbeta numerators, which the exchange
+        sums over the ranks itself."""
+        if not self.synced:
+            return local
+        g = self._gsums.get(key)
+        if g is None or g.numel() != local.numel():
+            g = self._gsums[key] = torch.zeros(local.numel(), dtype=torch.int64, device=local.device)
+        ops.sums_fold(local, g)
+        if dist.is_available() and dist.is_initialized():  # (no group: one process, the sum over it is g)
+            dist.all_reduce(g[:local.numel() // ops.NSHARD], op=dist.ReduceOp.SUM, group=self.sync[0])
+        return g
 
     def norm_desc(self, q, chsum, n):
         return BnNorm(ptr(q).value, self.X_range.desc, ptr(chsum).value, n, ops.f32(self.eps),
@@ -775,10 +809,10 @@ class Normalization_q(Layer_q):
         chsum = self._c.sums("chsum", ops.NSHARD * 2 * C, self.ctx)
         self.q = ops.quantize(X, self.X_range, OUT_I8, out=self._c.get("q", X.shape, torch.int8, dev), chsum=chsum,
                               C=C)
-        self.n = X.numel() // C
+        self.n = self.global_n(X.numel() // C)
         y = self._c.get("y", X.shape, torch.float32, dev)
         a = ChainFwd()
-        a.b1.nrm = self.norm_desc(self.q, chsum, self.n)
+        a.b1.nrm = self.norm_desc(self.q, self.global_sums("chsum", chsum), self.n)
         a.relu = 0
         a.y = y.data_ptr()
         a.rows, a.inner, a.C = rows, inner, C
@@ -806,7 +840,8 @@ class Normalization_q(Layer_q):
             dx = self._c.get("dx", grad.shape, torch.float32, dev)
             pix = grad.numel() // C
             ops.bn_bwd_a_wide(grad, NO_Q, None, None, self.grad_range.desc, self.q, G16, None, sums, pix, inner, C)
-            ops.bn_bwd_b_wide(G16, self.grad_range.desc, self.q, self.X_range.desc, self.ms, sums, self.n, dx, pix, C)
+            ops.bn_bwd_b_wide(G16, self.grad_range.desc, self.q, self.X_range.desc, self.ms,
+                              self.global_sums("sums", sums), self.n, dx, pix, C)
             return dx
         G = self._c.get("G", grad.shape, torch.int8, dev)
         self.grad_range.observe(grad.numel())
@@ -819,7 +854,8 @@ class Normalization_q(Layer_q):
         dx = self._c.get("dx", grad.shape, torch.float32, dev)
         # testing mode: mean / variance are constants, dX = Gq / sigma -- pass B with zero sums
         # (mg = mgx = 0 makes its ((g - mg) - xhat*mgx) / sigma exactly g / sigma)
-        bsums = sums if self.train else self._c.get("zsums", sums.shape, torch.int64, dev, zero=True)
+        bsums = (self.global_sums("sums", sums) if self.train
+                 else self._c.get("zsums", sums.shape, torch.int64, dev, zero=True))
         b = ChainBwdB(G.data_ptr(), self.grad_range.desc, self.q.data_ptr(), self.X_range.desc, self.ms.data_ptr(),
                       bsums.data_ptr(), self.n, dx.data_ptr(), None, NO_Q, None, rows, inner, C)
         ops.chain_bwd_b(b)
@@ -1172,7 +1208,8 @@ class ResidualBottleneck_q(ResidualBlock_q):
         n.q = n._c.get("q", shape, torch.int8, xq.device)
         ops.conv_fwd_igemm_q(xq, 1, conv.wf, conv.ksf, d, conv.X_range.desc, conv.W_range.desc, n.q, n.X_range,
                              n._chsum)
-        n.n = N * d.Ho * d.Wo
+        n._chsum = n.global_sums("chsum", n._chsum)  # SyncBN: the ranks' totals (the chain reads only these)
+        n.n = n.global_n(N * d.Ho * d.Wo)
         r.R = r._c.get("R", shape, torch.int8, xq.device)
         return n.q  # the chain needs only its shape
 
@@ -1184,7 +1221,8 @@ class ResidualBottleneck_q(ResidualBlock_q):
         C = y.shape[-1]
         n._chsum = n._c.sums("chsum", ops.NSHARD * 2 * C, ctx)
         n.q = ops.quantize(y, n.X_range, OUT_I8, out=n._c.get("q", y.shape, torch.int8, y.device), chsum=n._chsum, C=C)
-        n.n = y.numel() // C
+        n._chsum = n.global_sums("chsum", n._chsum)  # SyncBN: the ranks' totals (the chain reads only these)
+        n.n = n.global_n(y.numel() // C)
         r.R = r._c.get("R", y.shape, torch.int8, y.device)
 
     def _forward_fused(self, X):
@@ -1290,7 +1328,8 @@ class ResidualBottleneck_q(ResidualBlock_q):
                                r.dgamma, r.dbeta)
         conv_out.grad_range.observe(numel)
         gq = conv_out._c.get("gq16", G16.shape, torch.int16, G16.device)
-        ops.bn_bwd_b_wide_q(G16, n.grad_range.desc, n.q, n.X_range.desc, n.ms, sums, n.n, gq,
+        # SyncBN: pass B reads the ranks' totals; the local sums stay for the side stream's dgamma / dbeta
+        ops.bn_bwd_b_wide_q(G16, n.grad_range.desc, n.q, n.X_range.desc, n.ms, n.global_sums("sums", sums), n.n, gq,
                             conv_out.grad_range.desc, rows, inner, C)
         return gq
 

@@ -393,6 +393,20 @@ def bn_moments(nrm, C):
         call("lbt_bn_moments", _lib.ctypes.byref(nrm), int(C), stream())
 
 
+def sums_fold(part, total):
+    """SyncBN (Normalization_q.sync): the totals of a sharded [NSHARD][stride] int64 statistics buffer
+    into total[:stride] (lbt_sums_fold) -- nothing else of total is written."""
+    _check(part, torch.int64, "part")
+    _check(total, torch.int64, "total")
+    stride, rem = divmod(part.numel(), NSHARD)
+    if rem or stride == 0 or total.numel() < stride:
+        raise ValueError("part must be [%d][stride] and total hold at least stride elements, got %d and %d"
+                         % (NSHARD, part.numel(), total.numel()))
+    with _Timed("sums_fold_kernel", (NSHARD + 1) * stride * 8):
+        call("lbt_sums_fold", ptr(part), NSHARD, stride, ptr(total), stream())
+    return total
+
+
 def chain_fwd(desc):
     with _Timed("chain_fwd_kernel", _chain_fwd_bytes(desc)):
         call("lbt_bn_chain_fwd", _lib.ctypes.byref(desc), stream())

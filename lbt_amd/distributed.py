@@ -26,6 +26,12 @@ models with Dropout_q: a bias gradient travels as its numerator too (lbt_bias_gr
 GLOBAL tensor (base = rank * n: lbt_dropout_*_at), so the N-rank step equals the one-process step on the
 whole batch bit for bit (tests/test_dp_dropout_gpu.py).
 
+The BatchNorm statistics of such a model stay per rank unless sync_batchnorm(model) switches them to the
+global batch's: every Normalization_q then folds its exact int64 channel sums (forward) and pass-A sums
+(backward) to their totals (lbt_sums_fold) and all-reduces those 2C / 4C integers before the kernel that
+consumes them, and the N-rank step equals the ONE-process step on the whole batch bit for bit
+(tests/test_syncbn_layerwise_dp_gpu.py).
+
 Other layer-wise models (fp32-mode layers; biases without a declared rank) exchange dequantised
 gradients instead, an all-reduce SUM of
 
@@ -114,6 +120,47 @@ def float_mode_layer(model, biases=True):
         if var not in ok or getattr(owner, "fmode", False):
             return owner
     return None
+
+
+def sync_batchnorm(model, process_group=None, force=False):
+    """SyncBN for a layer-wise model: every Normalization_q takes the moments of the GLOBAL batch.
+
+    Sets ``sync = (process_group, world)`` on every Normalization_q of ``model`` (Model._walk) and
+    ``model.sync_bn = True``; returns ``model``. While such a layer trains, the exact int64 channel sums
+    behind its moments and the exact int64 pass-A sums behind its input gradient are folded to their totals
+    (lbt_sums_fold) and summed over the ranks (one all-reduce of 2C, one of 4C int64 per layer and step)
+    before the kernel that consumes them -- so with the exact int64 exchange the same script on N ranks
+    leaves the parameters, momentum, exponents and BN running statistics of one process on the whole
+    batch, bit for bit. ``world`` is the group's size. At world 1 this is a no-op that leaves
+    ``model.sync_bn`` False, unless ``force`` keeps the folds and collectives (tests of the path: a sum over
+    one rank is the identity; without a process group only the folds run).
+
+    Refused before anything is launched: a FusedResNet (TypeError: it has ``sync_bn=`` of its own), a
+    float-mode Normalization_q (NotImplementedError: its statistics are fp32 partials, not integers),
+    world > 1 without an initialised process group (RuntimeError), a model that already ran a forward
+    (RuntimeError: captured graphs and warmed-up buffers would not hold the collectives)."""
+    from .dfxp.layers import Normalization_q
+    if hasattr(model, "set_exchange") or not hasattr(model, "_walk"):
+        raise TypeError("sync_batchnorm takes a layer-wise Model; %s has sync_bn= of its own"
+                        % type(model).__name__)
+    norms = [l for l in model._walk() if isinstance(l, Normalization_q)]
+    for n in norms:
+        if n.fmode:
+            raise NotImplementedError("SyncBN of the float-mode layer %r: its statistics are fp32 partial sums, "
+                                      "not integers (bits <= 8 and grad_bits <= 16 run on integer sums)" % n.name)
+    ready = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(process_group) if ready else 1
+    if not ready and model.ctx.world_size > 1:
+        raise RuntimeError("sync_batchnorm at world %d needs an initialised process group "
+                           "(torch.distributed.init_process_group)" % model.ctx.world_size)
+    if getattr(model, "logits", None) is not None or any(hasattr(n, "q") for n in norms):
+        raise RuntimeError("sync_batchnorm after the model ran a forward: switch it before the first step")
+    if world == 1 and not force:
+        return model
+    for n in norms:
+        n.sync = (process_group, world)
+    model.sync_bn = True
+    return model
 
 
 def allreduce_comm(comm, group=None):

@@ -6,6 +6,8 @@ sparse softmax cross-entropy (``:30-32``) and the manual backward from d loss / 
 ``:371-470``; ``PI_MNIST_Model`` / ``MNIST_Model`` / ``CIFAR10_Model`` / ``CIFAR10_VGG_Model`` mirror
 ``:57-368``. Inputs are NHWC fp32 CUDA tensors (``[B, 784]`` for the PI model), labels int32.
 """
+import contextlib
+
 import torch
 
 from . import dynamic_fixed_point as L
@@ -132,6 +134,28 @@ class Model:
 
     def _norm_layers(self):
         return [l for l in self._walk() if isinstance(l, L.Normalization_q)]
+
+    # SyncBN (lbt_amd.distributed.sync_batchnorm sets it): every Normalization_q takes the moments of the
+    # GLOBAL batch, so N ranks on the shards train what one process trains on the whole batch
+    sync_bn = False
+
+    @contextlib.contextmanager
+    def sync_suspended(self):
+        """Inside: every Normalization_q takes its own batch's statistics (no fold, no collective), as
+        before sync_batchnorm -- for a batch every rank holds whole (Trainer.evaluate: a rank's moments
+        of the whole test batch ARE the one process's). The layers' sync is restored on the way out,
+        also when the body raises."""
+        saved = [(n, n.sync) for n in self._norm_layers()]
+        flag = self.sync_bn
+        for n, _ in saved:
+            n.sync = None
+        self.sync_bn = False
+        try:
+            yield self
+        finally:
+            for n, s in saved:
+                n.sync = s
+            self.sync_bn = flag
 
     def _mode_layers(self):
         """The layers with a training / testing branch (``tf.cond(self.train, ..)``)."""

@@ -21,6 +21,11 @@ MI355X-native execution:
     samples is bit-identical to one process on the N*b batch.
   - layer-wise models: dequantised fp32 gradients + counters folded into exact fp32 pairs, one
     fp32 all-reduce (gscale = 1/world).
+  - layer-wise models with ``lbt_amd.distributed.sync_batchnorm(model)``: every Normalization_q sums its
+    exact integer statistics over the ranks (lbt_sums_fold + one small all-reduce, forward and backward), so
+    on the exact int64 exchange -- required: the fp32 one is refused -- N ranks on the shards equal one
+    process on the whole batch bit for bit. Those collectives sit inside the step: captured with it under
+    RCCL, eager steps under gloo; ``evaluate()`` suspends them (every rank holds each test batch whole).
   - ``DfxpContext(world_size=N, rank=r)``: the plain models with ``Dropout_q`` train data-parallel on
     the exact int64 exchange (bias numerators included), each rank drawing its shard's bits of the
     global batch's dropout mask: N ranks on the shards equal one process on the whole batch.
@@ -37,6 +42,7 @@ MI355X-native execution:
   update -- which zeroes the overflow counters that drove its range decisions -- and ``lbt_summary_commit``
   after it (``lbt_amd/summary.py``). Every other step replays the graph it replays without summaries.
 """
+import contextlib
 import os
 import sys
 
@@ -196,6 +202,13 @@ class Trainer:
         self._lw_exact = (self.dp and not exact and D.exact_layerwise_ok(model, biases=ranked)
                           and (os.environ.get("LBT_EXACT_LAYERWISE", "1") == "1"
                                or (ranked and self._has_dropout(model))))
+        if self.dp and not exact and not self._lw_exact and getattr(model, "sync_bn", False):
+            # global BN statistics promise one process's bits: dequantised fp32 gradients summed in the
+            # collective's order cannot keep that promise
+            raise NotImplementedError("a layer-wise model with sync_batchnorm trains data-parallel on the exact "
+                                      "int64 exchange only (integer-coded parameters, no bias without a declared "
+                                      "rank, LBT_EXACT_LAYERWISE not 0): the fp32 exchange cannot give SyncBN's "
+                                      "bit-for-bit guarantee")
         if self.dp and not exact and not self._lw_exact:
             n = sum(getattr(o, v).numel() for o, v, _ in model.param_slots())
             self.comm = D.make_comm_buffer(n, len(self.ctx.quantizers), self.ctx.device)
@@ -748,6 +761,8 @@ class Trainer:
                     p = self._eval[key]
                 else:
                     p = m
+                if not fused:  # (as evaluate: a layer-wise model's sums arena is this trainer's to clear)
+                    self.ctx.zero_sums()
                 logits = p.forward(Xb)
                 loss = p.compute_loss(yb)
                 accs.append((logits.argmax(dim=1).to(torch.int32) == yb).float().mean())
@@ -783,6 +798,16 @@ class Trainer:
                 self._eval[n] = FusedResNet(m.model)
             return self._eval[n], False
         return m, True
+
+    def _unsynced(self):
+        """The context the whole-batch test loops run in: a layer-wise model with sync_batchnorm suspends
+        its synchronisation (Model.sync_suspended, restored also when the loop raises), because every rank
+        forwards every test batch whole -- a rank's moments of that batch are the one process's, and a sum
+        over the ranks would count it world times. Anything else: nothing."""
+        m = self.model
+        if getattr(m, "sync_bn", False) and hasattr(m, "sync_suspended"):
+            return m.sync_suspended()
+        return contextlib.nullcontext()
 
     def _shards_eval(self, testing):
         """Whether evaluate() splits its test batches over the ranks: only where the rows a rank computes
@@ -909,29 +934,39 @@ class Trainer:
         return value and side effects (_evaluate_device).
         Under a process group of several ranks every rank runs the whole loop and gets the same result,
         except where a test batch can be split by rows exactly (_evaluate_sharded): the training-mode loop
-        of a FusedResNet trained with sync_bn=True, and evaluate(testing=True) of a FusedResNet."""
+        of a FusedResNet trained with sync_bn=True, and evaluate(testing=True) of a FusedResNet. A layer-wise
+        model with sync_batchnorm runs the whole loop on every rank with its synchronisation suspended
+        (_unsynced): a rank's moments of the whole test batch are the one process's.
+        A layer-wise model's BN statistics are added into the context's sums arena, which this trainer
+        clears once per training step: the loops clear it before each test batch's forward as well."""
         if isinstance(X, DeviceDataset) and y is not None:
             raise TypeError("a DeviceDataset carries its labels: evaluate(ds, batch_size=..., testing=...)")
         if self._shards_eval(testing):
             return self._evaluate_sharded(X, y, batch_size, testing)
         if isinstance(X, DeviceDataset):
-            return self._evaluate_device(X, batch_size, testing)
+            with self._unsynced():  # (a layer-wise SyncBN model: every rank holds the test batch whole)
+                return self._evaluate_device(X, batch_size, testing)
         if testing:
             return self._evaluate_testing(X, y, batch_size)
         dev = self.ctx.device
         saved = self.ctx.counts.clone()
         saved_nelem = self.ctx.nelem.clone()  # an eval plan's build declares its own element counts
         acc_sum, loss_sum, nb, shared = 0.0, 0.0, 0, False
-        for b in range(0, len(X), batch_size):
-            Xb = torch.as_tensor(X[b:b + batch_size], dtype=torch.float32).to(dev).contiguous()
-            yb = torch.as_tensor(y[b:b + batch_size], dtype=torch.int32).to(dev)
-            m, shared = self._eval_model(len(Xb))
-            logits = m.forward(Xb)
-            loss = m.compute_loss(yb)
-            acc = (logits.argmax(dim=1).to(torch.int32) == yb).float().mean()
-            acc_sum += float(acc.item())
-            loss_sum += float(loss.item())
-            nb += 1
+        with self._unsynced():  # (a layer-wise SyncBN model: every rank holds the test batch whole)
+            for b in range(0, len(X), batch_size):
+                Xb = torch.as_tensor(X[b:b + batch_size], dtype=torch.float32).to(dev).contiguous()
+                yb = torch.as_tensor(y[b:b + batch_size], dtype=torch.int32).to(dev)
+                m, shared = self._eval_model(len(Xb))
+                if shared:
+                    # a layer-wise model's BN channel sums are ADDED into the arena this trainer clears once
+                    # per training step: each test batch starts from zeros too, not from the last step's sums
+                    self.ctx.zero_sums()
+                logits = m.forward(Xb)
+                loss = m.compute_loss(yb)
+                acc = (logits.argmax(dim=1).to(torch.int32) == yb).float().mean()
+                acc_sum += float(acc.item())
+                loss_sum += float(loss.item())
+                nb += 1
         self.ctx.counts.copy_(saved)
         self.ctx.nelem.copy_(saved_nelem)
         # the quantisers' cached counts now describe the eval plan, not ctx.nelem: forget them so
