@@ -1112,10 +1112,43 @@ int lbt_summary_commit(const lbt_summary* s, void* stream);
 int lbt_eval_tally(const float* logits, const int32_t* labels, int32_t B, int32_t classes, int64_t* row /* [2] */,
                    void* stream);
 
+/* ---- Range calibration (range_scan.hip): the range update_range would settle on for one tensor, from
+ * one read of it. For a quantiser of bits < 32 and target t fed n fp32 elements x, with lo = bits - 31 and
+ * hi = bits - 1 (the controller's clamp):
+ *   c1(I) = #{x >= 2^I} + #{x < -2^I}    (the controller's first overflow count at range I, exactly: the
+ *                                          multiplier is a power of two; its second count is c1(I - 1))
+ *   I*    = min{I in [lo, hi] : (float)c1(I) / nelem <= t}, or hi if there is none
+ * I* is the one range the controller leaves where it is on that tensor. If c1(lo) == 0 (an all-zero tensor:
+ * a fresh beta or bias) the range is KEPT, not sent to lo.
+ * Per element the largest overflowing I is the biased exponent - 127, minus 1 for a negative value with a
+ * zero mantissa; +-0, denormals and NaN overflow nowhere, +-inf everywhere.
+ *
+ * lbt_dfxp_range_scan ADDS to table[I + 30], I = -30 .. 30 (LBT_RANGE_BINS entries), the number of elements
+ * of x[0..n) whose LARGEST overflowing range is I (I = 30 also takes everything above it): a histogram, so
+ * c1(I) is the sum of the entries from I + 30 up (lbt_dfxp_range_pick forms it). The caller zeroes the table;
+ * two calls on one table give the counts of both tensors. x is read once, 16 bytes per lane between a scalar
+ * head and tail: any 4-byte alignment, any n >= 0 (n == 0: nothing is launched). Integer sums only: the
+ * same x gives the same table in every run. LBT_EINVAL before any HIP call: n < 0 or n > 2^40, a NULL x or
+ * table with n > 0, x not 4-byte aligned.
+ *
+ * lbt_dfxp_range_pick: job j (one wave) takes slot s = slots[j] (a HOST array, passed to the kernel by value,
+ * LBT_RANGE_PICK_JOBS per launch), sums tables[s * LBT_RANGE_BINS ..] from the top into c1, reads bits[s], target[s] and nelem[s] (the
+ * float lbt_dfxp_range_update divides by) and writes kept[s] = 1 and nothing else when c1(lo) == 0, else
+ * kept[s] = 0 and exps[s] = I* (the quotient and comparison of lbt_dfxp_range_update). A slot of bits >= 32
+ * is left alone, its kept flag too. tables / exps / bits / target / nelem / kept: device arrays of nslots
+ * slots. LBT_EINVAL before any HIP call: njobs < 0, nslots < 0, a NULL pointer with njobs > 0, a slot
+ * outside [0, nslots). (Added under ABI 24.)                                                          */
+#define LBT_RANGE_BINS 61
+#define LBT_RANGE_PICK_JOBS 256
+int lbt_dfxp_range_scan(const float* x, int64_t n, uint64_t* table /* [LBT_RANGE_BINS] */, void* stream);
+int lbt_dfxp_range_pick(const uint64_t* tables, const int32_t* slots, int32_t njobs, int32_t* exps,
+                        const int32_t* bits, const float* target, const float* nelem, int32_t nslots,
+                        int32_t* kept, void* stream);
+
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
  * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather,
- * lbt_summary_*, lbt_augment_flip_crop_at and lbt_eval_tally are additions under the same number: every
+ * lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
  * earlier signature and result stands.                                                              */
 int lbt_abi_version(void);
 

@@ -199,6 +199,7 @@ class Summary(ctypes.Structure):
 
 
 SUMMARY_CHUNK = 16384  # LBT_SUMMARY_CHUNK
+RANGE_BINS = 61  # LBT_RANGE_BINS: a calibration table's entries, I = -30 .. 30
 
 _P = c_void_p
 _SIGS = {
@@ -345,6 +346,8 @@ _SIGS = {
     "lbt_summary_scratch_bytes": [c_int32, c_int64],
     "lbt_summary_record": [ctypes.POINTER(Summary), _P],
     "lbt_summary_commit": [ctypes.POINTER(Summary), _P],
+    "lbt_dfxp_range_scan": [_P, c_int64, _P, _P],
+    "lbt_dfxp_range_pick": [_P, ctypes.POINTER(c_int32), c_int32, _P, _P, _P, _P, c_int32, _P, _P],
 }
 EXPORTED = sorted(_SIGS)
 

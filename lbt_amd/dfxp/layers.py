@@ -832,6 +832,7 @@ class Normalization_q(Layer_q):
             return dx
         rows, inner = ops.rows_inner(tuple(grad.shape))
         sums = self._c.sums("sums", ops.NSHARD * 4 * C, self.ctx)
+        self.ctx.feed(self.grad_range, grad)
         if self.grad_bits > 8:  # 16-bit gradient codes (config 4)
             if not self.train:
                 raise NotImplementedError("Normalization_q testing-mode backward with > 8-bit gradient codes")
@@ -916,6 +917,7 @@ class Rescale_q(Layer_q):
             return y
         self.R = self._c.get("R", X.shape, torch.int8, dev)
         y = self._c.get("y", X.shape, torch.float32, dev)
+        self.ctx.feed(self.X_range, X)
         self.X_range.observe(X.numel())
         a = ChainFwd()
         a.b1.xin = X.data_ptr()
@@ -941,6 +943,7 @@ class Rescale_q(Layer_q):
                       ptr(self.dgamma), ptr(self.dbeta), _lib.stream())
             return dx
         sums = self._c.sums("sums", ops.NSHARD * 4 * C, self.ctx)
+        self.ctx.feed(self.grad_range, grad)
         self.grad_range.observe(grad.numel())
         if self.grad_bits > 8:  # 16-bit gradient codes (config 4)
             ops.bn_bwd_a_wide(grad, self.grad_range.desc, self.R, self.gb[:C], NO_Q, None, None, dx, sums,
@@ -1141,13 +1144,18 @@ class ResidualBottleneck_q(ResidualBlock_q):
                                       and c.igemm_w and not c.use_bias for c in convs))
         return self._fuse
 
+    def _unfused_now(self):
+        """The Sequential_q composition runs: the block does not fuse, or a calibration pass needs every
+        quantiser's fp32 input written (DfxpContext.calibrating; the fused schedule keeps them in registers)."""
+        return not self._fusable() or self.residual.layers[0].ctx.calibrating_now
+
     def forward(self, X):
-        if not self._fusable():
+        if self._unfused_now():
             return super().forward(X)
         return self._forward_fused(X)
 
     def backward(self, grad, stochastic=True):
-        if not self._fusable():
+        if self._unfused_now():
             return super().backward(grad, stochastic)
         with backward_scope():  # dW / dgamma / dbeta of the side stream are joined by the outermost backward
             return self._backward_fused(grad)
@@ -1540,7 +1548,7 @@ class Dropout_q(Layer_q):
     def fused(self):
         """The next layer's input quantiser applies this dropout (integer-code layers only)."""
         return (DROPOUT_FUSE and self.active and self._feeds is not None
-                and not getattr(self._feeds, "fmode", False))
+                and not getattr(self._feeds, "fmode", False) and not self.ctx.calibrating_now)
 
     @property
     def folds_relu(self):

@@ -64,6 +64,39 @@ def new_sums(C, per_shard, device):
     return torch.zeros(NSHARD * per_shard * C, dtype=torch.int64, device=device)
 
 
+# ----------------------------------------------------------------------------- range calibration
+def range_scan(x, table):
+    """table[I + 30] += the number of elements of x whose largest overflowing range is I, I = -30 .. 30
+    (lbt_dfxp_range_scan): the sum of the entries from I up is c1(I), how many elements overflow at range I.
+    table: int64 [RANGE_BINS], zeroed by the caller; x: fp32, any 4-byte alignment."""
+    _check(x, torch.float32, "x")
+    _check(table, torch.int64, "table")
+    if table.numel() != _lib.RANGE_BINS:
+        raise ValueError("table must hold %d entries, got %d" % (_lib.RANGE_BINS, table.numel()))
+    with _Timed("range_scan_kernel", 4 * x.numel()):
+        call("lbt_dfxp_range_scan", ptr(x), x.numel(), ptr(table), stream())
+    return table
+
+
+def range_pick(tables, slots, exps, bits, target, nelem, kept):
+    """The calibrated range of every slot in `slots` (host ints) from its table (lbt_dfxp_range_pick):
+    exps[s] = I*, or kept[s] = 1 and exps[s] untouched where nothing reaches the lowest range. tables:
+    int64 [nslots, RANGE_BINS]; exps / bits / target / nelem / kept: the per-slot device arrays."""
+    _check(tables, torch.int64, "tables")
+    _check(exps, torch.int32, "exps")
+    _check(bits, torch.int32, "bits")
+    _check(target, torch.float32, "target")
+    _check(nelem, torch.float32, "nelem")
+    _check(kept, torch.int32, "kept")
+    nslots = tables.numel() // _lib.RANGE_BINS
+    if min(exps.numel(), bits.numel(), target.numel(), nelem.numel(), kept.numel()) < nslots:
+        raise ValueError("range_pick: a per-slot array is shorter than the %d tables" % nslots)
+    slots = [int(s) for s in slots]
+    arr = (ctypes.c_int32 * max(len(slots), 1))(*slots)
+    call("lbt_dfxp_range_pick", ptr(tables), arr, len(slots), ptr(exps), ptr(bits), ptr(target), ptr(nelem), nslots,
+         ptr(kept), stream())
+
+
 # ----------------------------------------------------------------------------- quantiser
 def quantize(x, q, kind, out=None, chsum=None, C=0, stats=True):
     """weight_quantization of x with quantiser q (dynamic_fixed_point.py:4-45) -> codes in `kind`."""
@@ -71,6 +104,7 @@ def quantize(x, q, kind, out=None, chsum=None, C=0, stats=True):
     rows, inner = rows_inner(tuple(x.shape))
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype(kind), device=x.device)
+    q.ctx.feed(q, x)  # inside DfxpContext.calibrating(): the range is set from x first
     if stats:
         q.observe(x.numel())
     desc = q.desc if stats else q.desc_nostats()
@@ -92,6 +126,7 @@ def quantize_weight(w, q, w_hwio=None, wf=None, ksf=0, wd=None, ksd=0, colsum=No
         KW = Cin = 1
     else:
         KH, KW, Cin, Cout = w.shape
+    q.ctx.feed(q, w)
     q.observe(w.numel())
     call("lbt_dfxp_quantize_weight", ptr(w), KH, KW, Cin, Cout, q.desc, ptr(w_hwio), ptr(wf), int(ksf), ptr(wd),
          int(ksd), ptr(colsum), stream())
@@ -570,6 +605,9 @@ def dropout_quantize(x, keep, did, q, kind, out=None, relu=False, desc=None):
     rows, inner = rows_inner(tuple(x.shape))
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype(kind), device=x.device)
+    if q.ctx.calibrating_now:  # the quantiser's fp32 input has to exist to be scanned: the two launches
+        y = dropout_fwd(x, torch.empty_like(x), keep, q.ctx, did, relu=relu)
+        return quantize(y, q, kind, out=out)
     q.observe(x.numel())
     base = q.ctx.mask_base(x.numel())
     vec = inner % 4 == 0 and inner >= 64 and x.data_ptr() % 16 == 0 and not (base or 0) % 4

@@ -99,6 +99,32 @@ class DfxpContext:
         self.sums_managed = False
         self.params_ready = False  # a model's batched prologue quantised every participating parameter  # True while a Trainer zeroes the arena once per step
 
+    # ---- range calibration: every quantiser's range set from the tensor it is fed (lbt_dfxp_range_scan /
+    # _pick) to the value update_range leaves unchanged on that tensor, then quantised with it in the same
+    # call. The unchanged controller takes over from there.
+    _cal = None
+
+    @property
+    def calibrating_now(self):
+        """True inside ``calibrating()``: layers take the routes that write every quantiser's fp32 input."""
+        return self._cal is not None
+
+    def calibrating(self, params=()):
+        """Context manager of one calibration pass. params: [(quantiser, fp32 tensor)] that do not depend on
+        the batch (weights, gammas, betas, biases) -- scanned on entry, one scan per tensor and one batched
+        pick, so the model's batched parameter prologue finds their ranges set. Inside, ``feed`` sets every
+        other quantiser when it meets its input. Yields the record: ``.result()`` after the pass is
+        {"set": {name: I}, "kept": [names], "unfed": [names]} (kept: nothing of the tensor reaches the
+        lowest range, e.g. an all-zero beta -- its range stays). Outside any graph capture."""
+        return _Calibration(self, params)
+
+    def feed(self, q, x):
+        """Inside ``calibrating()``: set q's range from its fp32 input x (scan + pick, two launches) before
+        the caller quantises x. Outside: nothing. A quantiser fed twice in one pass raises RuntimeError."""
+        cal = self._cal
+        if cal is not None and q.bits < 32:
+            cal.feed(q, x)
+
     def shard_masks(self):
         """Context manager the data-parallel Trainer holds around a training step's forward and backward:
         inside it ``mask_base`` is the shard's offset, outside it (evaluation, a single process) 0."""
@@ -244,6 +270,95 @@ class DfxpContext:
             raise ValueError("quantiser layout mismatch")
         self.exps.copy_(sd["exps"])
         self.step.copy_(sd["step"])
+
+
+class _Calibration:
+    """One pass of ``DfxpContext.calibrating``. The tables [capacity, RANGE_BINS] and the kept flags are the
+    context's, allocated on the first pass and zeroed on entry."""
+
+    def __init__(self, ctx, params):
+        self.ctx, self.params = ctx, list(params)
+        self.fed = {}        # slot -> quantiser, in feeding order
+        self.from_params = set()
+        self._kept = None
+
+    def __enter__(self):
+        ctx = self.ctx
+        if ctx._cal is not None:
+            raise RuntimeError("DfxpContext.calibrating() is already active on this context")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DfxpContext.calibrating() inside a graph capture: calibration reads its result back")
+        if getattr(ctx, "_cal_tables", None) is None:
+            ctx._cal_tables = torch.zeros(ctx.capacity * _lib.RANGE_BINS, dtype=torch.int64, device=ctx.device)
+            ctx._cal_kept = torch.zeros(ctx.capacity, dtype=torch.int32, device=ctx.device)
+        else:
+            ctx._cal_tables.zero_()
+            ctx._cal_kept.zero_()
+        ctx._cal = self
+        from .dfxp import layers
+        self._side, layers.SIDE_STREAM = layers.SIDE_STREAM, False  # one stream: nothing here is timed
+        try:
+            slots = []
+            for q, x in self.params:
+                if q.bits >= 32:
+                    continue
+                self._scan(q, x)
+                self.from_params.add(q.slot)
+                slots.append(q.slot)
+            self._pick(slots)
+        except BaseException:
+            self.__exit__(True, None, None)
+            raise
+        return self
+
+    def __exit__(self, et, ev, tb):
+        from .dfxp import layers
+        self.ctx._cal = None
+        layers.SIDE_STREAM = self._side
+        if et is None:
+            self._kept = self.ctx._cal_kept[: len(self.ctx.quantizers)].cpu().tolist()
+            self._exps = self.ctx.exps[: len(self.ctx.quantizers)].cpu().tolist()
+        return False
+
+    def _table(self, q):
+        return self.ctx._cal_tables[q.slot * _lib.RANGE_BINS:(q.slot + 1) * _lib.RANGE_BINS]
+
+    def _scan(self, q, x):
+        from .dfxp import ops
+        if q.slot in self.fed:
+            raise RuntimeError("calibration: quantiser %r is fed twice in one pass (a reused layer?)" % q.name)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("calibration: quantiser %r is fed a tensor that is not contiguous fp32" % q.name)
+        self.fed[q.slot] = q
+        q.observe(x.numel())
+        ops.range_scan(x, self._table(q))
+
+    def _pick(self, slots):
+        from .dfxp import ops
+        c = self.ctx
+        if slots:
+            ops.range_pick(c._cal_tables, slots, c.exps, c.bits, c.target, c.nelem, c._cal_kept)
+
+    def feed(self, q, x):
+        if q.slot in self.from_params:
+            return  # set on entry from the parameter tensor itself
+        self._scan(q, x)
+        self._pick([q.slot])
+
+    def result(self):
+        if self._kept is None:
+            raise RuntimeError("the calibration pass has not finished")
+        out = {"set": {}, "kept": [], "unfed": []}
+        for q in self.ctx.quantizers:
+            if q.bits >= 32:
+                continue
+            if q.slot not in self.fed:
+                out["unfed"].append(q.name)
+            elif self._kept[q.slot]:
+                out["kept"].append(q.name)
+            else:
+                out["set"][q.name] = int(self._exps[q.slot])
+        return out
 
 
 class _ShardMasks:

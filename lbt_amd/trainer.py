@@ -477,6 +477,99 @@ class Trainer:
             bn.X_mean_running.copy_(m)
             bn.X_var_running.copy_(v)
 
+    # -- range calibration -------------------------------------------------------------------
+    @staticmethod
+    def _param_quantizers(root):
+        """[(quantiser, parameter tensor)] of every layer of the layer-wise model: what does not depend on
+        the batch (Conv2d_q / Dense_q W and b, Rescale_q gamma and beta)."""
+        out, seen = [], set()
+
+        def walk(layer):
+            if id(layer) in seen:
+                return
+            seen.add(id(layer))
+            for rng, var in (("W_range", "W"), ("g_range", "gamma")):
+                if hasattr(layer, rng) and hasattr(layer, var):
+                    out.append((getattr(layer, rng), getattr(layer, var)))
+            if hasattr(layer, "b_range"):
+                out.append((layer.b_range, layer.beta if hasattr(layer, "beta") else layer.b))
+            for attr in ("layers", "residual", "shortcut"):
+                sub = getattr(layer, attr, None)
+                for l in (sub if isinstance(sub, (list, tuple)) else [sub] if sub is not None else []):
+                    walk(l)
+        for layer in root.layers:
+            walk(layer)
+        return out
+
+    def calibrate(self, X, y):
+        """Set every quantiser's range from one batch (X, y: device tensors as step() takes them): one
+        forward, loss and backward of the layer-wise model inside ``DfxpContext.calibrating`` -- a fused
+        plan's ``model.model``, which shares every quantiser and parameter -- on a side stream outside any
+        capture, as the warm-up runs. Each range lands where update_range leaves it on this batch, so the
+        controller starts from its fixed point instead of the reference's I = 2. Everything else the pass
+        touches is put back: overflow counters zeroed, the noise step, BN running statistics, element
+        counts, parameters, accumulators, gradients, summaries and ``global_step`` as before; the next
+        step draws the noise and masks this pass saw. Before the first step or between steps (captured
+        graphs read the exponents from device memory). Returns {"set": {name: I}, "kept": [names],
+        "unfed": [names]}: kept ranges were left (nothing of the tensor reaches the lowest range -- a
+        zero beta or bias), unfed quantisers met no tensor."""
+        world = dist.get_world_size(self.pg) if (dist.is_available() and dist.is_initialized()) else 1
+        if max(world, self.world, self.ctx.world_size) > 1:
+            raise NotImplementedError("calibrate() under a process group of %d ranks: each rank would set its own "
+                                      "ranges from its shard (the ranks' tables are not summed yet)"
+                                      % max(world, self.world, self.ctx.world_size))
+        ctx = self.ctx
+        root = getattr(self.model, "model", self.model)
+        if not hasattr(root, "forward") or not hasattr(root, "backward"):
+            raise TypeError("calibrate() needs a layer-wise model (or a plan over one)")
+        torch.cuda.synchronize()
+        bns = self._bn_layers()
+        saved_bn = [(bn.X_mean_running.clone(), bn.X_var_running.clone()) for bn in bns]
+        saved_nelem = ctx.nelem.clone()
+        saved_qn = [q._nelem for q in ctx.quantizers]
+        saved_g = self.flat.g.clone()
+        saved_step = ctx.step.clone()
+        own = root is not self.model
+        had_prologue = getattr(root, "_pro", None) is not None
+        if own:
+            # a plan's step clears the arena it found when it was built: the layer-wise model's reduction
+            # buffers live in an arena of this pass's own, so no step ever pays for them
+            main = (ctx.sums_arena, ctx._sums_used, ctx._extra_arenas)
+            if getattr(self, "_cal_arena", None) is None:
+                self._cal_arena = (torch.zeros(1 << 20, dtype=torch.int64, device=ctx.device), 0, [])
+            ctx.sums_arena, ctx._sums_used, ctx._extra_arenas = self._cal_arena
+        params = self._param_quantizers(root)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        try:
+            with torch.cuda.stream(s):
+                ctx.zero_sums()  # (buffers carved later come from memory nothing has written: zeros)
+                with ctx.calibrating(params) as cal:
+                    root.forward(X)
+                    root.compute_loss(y)
+                    root.backward()
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+        finally:
+            if own:
+                self._cal_arena = (ctx.sums_arena, ctx._sums_used, ctx._extra_arenas)
+                ctx.sums_arena, ctx._sums_used, ctx._extra_arenas = main
+            ctx.counts.zero_()
+            ctx.step.copy_(saved_step)
+            ctx.nelem.copy_(saved_nelem)
+            for q, n in zip(ctx.quantizers, saved_qn):
+                q._nelem = n
+            if not own and not had_prologue:
+                # the parameter prologue this pass built declared its element counts once, and they were
+                # just put back: the model's next forward builds it (and declares them) again
+                root._pro = None
+            self.flat.g.copy_(saved_g)
+            for bn, (m, v) in zip(bns, saved_bn):
+                bn.X_mean_running.copy_(m)
+                bn.X_var_running.copy_(v)
+            torch.cuda.synchronize()
+        return cal.result()
+
     def _capture(self, X, y, rec=False):
         m = self.model
         fresh = not self._gflag or self._static is None or self._static[0].shape != X.shape
