@@ -949,6 +949,41 @@ int lbt_augment_flip_crop_at(const float* x, float* y, int32_t N, int32_t H, int
 int lbt_batch_gather(const void* data, int32_t src_kind, const double* mean, const int32_t* labels, int64_t n_data,
                      const int32_t* idx, int64_t first, float* X, int32_t* y, int32_t B, int32_t H, int32_t W,
                      int32_t C, int32_t pad, int32_t flip, int64_t base, uint64_t seed, uint64_t counter, void* stream);
+/* The ImageNet input pipeline (data.py:58-93) from a dataset held on the device, one launch per batch:
+ * RandomResizedCrop(size, scale, ratio) + RandomHorizontalFlip (augment != 0) or the central (ch, cw) box
+ * (augment == 0: Resize + CenterCrop on a store resized offline), a bilinear resample (half-pixel centres, no
+ * antialiasing) of the box to Ho x Wo, ToTensor and Normalize(mean, std). data is uint8 [n_data][Hs][Ws][C],
+ * X fp32 [B][Ho][Wo][C]; sample b takes source s = idx ? idx[b] : first + b and y[b] = labels[s]. Defined in
+ * integers, so every implementation agrees bit for bit (tests/resized_crop_oracle.py restates it in numpy).
+ * The caller prepares, once: a_lo = max(1, ceil(scale0 * Hs * Ws)), a_hi = max(a_lo, floor(scale1 * Hs * Ws));
+ * ratio_q16 [256] (device uint32), entry k = rint(65536 * exp(log r0 + (k + 0.5) / 256 * (log r1 - log r0)));
+ * q_lo = rint(65536 * r0), q_hi = rint(65536 * r1); shift [C] = 65536 * 255 * mean[c] and scale_c [C] =
+ * 1 / (65536 * 255 * std[c]) (device float64).
+ *   box, augment: for attempt t = 0..9, r = Philox of (base + b, "RRC!" + t, counter; seed); a = a_lo + r0 %
+ *     (a_hi - a_lo + 1), q = ratio_q16[r1 >> 24], w = (isqrt((4 a q) >> 16) + 1) >> 1, h = (isqrt(((4 a) <<
+ *     16) / q) + 1) >> 1 (64-bit unsigned, isqrt the floor of the root; q == 0 rejects); accepted when 1 <= w
+ *     <= Ws and 1 <= h <= Hs, with top = r2 % (Hs - h + 1), left = r3 % (Ws - w + 1). After ten rejections:
+ *     Ws * 65536 < q_lo * Hs: w = Ws, h = min(Hs, (2 Ws 65536 + q_lo) / (2 q_lo)); Ws * 65536 > q_hi * Hs:
+ *     h = Hs, w = min(Ws, (2 Hs q_hi + 65536) >> 17); else the whole image (h, w at least 1); top = (Hs - h)
+ *     / 2, left = (Ws - w) / 2. flip = Philox of (base + b, "AUG!", counter; seed) r0 & 1, lbt_batch_gather's.
+ *   box, not augmenting: h = ch, w = cw, top = (Hs - ch) / 2, left = (Ws - cw) / 2, no flip.
+ *   row i: n = clamp((2i + 1) h - Ho, 0, (h - 1) 2Ho), y0 = n / 2Ho, fy = ((n - y0 2Ho) 256 + Ho) / 2Ho, y1 =
+ *     min(y0 + 1, h - 1); column j (Wo - 1 - j when flipped) the same with w and Wo.
+ *   t = (256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11)   int32, <= 255 * 65536
+ *   X = (float)(((double)t - shift[c]) * scale_c[c])
+ * base as in lbt_batch_gather: two shards with their bases equal one batch. LBT_EINVAL before any HIP call: a
+ * NULL data / labels / X / y / ratio_q16 / shift / scale_c; B / Hs / Ws / C / Ho / Wo / n_data <= 0; Hs, Ws,
+ * Ho or Wo > 8192; Hs*Ws*C or Ho*Wo*C >= 2^31; a_lo < 1, a_hi < a_lo, a_hi > Hs*Ws; q_lo < 1, q_hi < q_lo,
+ * q_hi >= 2^32; ch outside [1, Hs] or cw outside [1, Ws]; base < 0 or base + B > 2^32; idx == NULL with first
+ * < 0 or first + B > n_data. An idx value outside [0, n_data) reads nothing: a zero image and label -1.
+ * 16-byte stores when (Wo*C) % 4 == 0 and X is 16-byte aligned, else 4-byte: the same values. (Added under
+ * ABI 24.)                                                                                              */
+int lbt_batch_resized_crop(const uint8_t* data, const int32_t* labels, int64_t n_data, const int32_t* idx,
+                           int64_t first, float* X, int32_t* y, int32_t B, int32_t Hs, int32_t Ws, int32_t C,
+                           int32_t Ho, int32_t Wo, int32_t augment, int64_t a_lo, int64_t a_hi,
+                           const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, int32_t ch, int32_t cw,
+                           const double* shift, const double* scale_c, int64_t base, uint64_t seed, uint64_t counter,
+                           void* stream);
 
 /* Diagnostics: counts (atomically into *bad) the i < n where the BN kernels' division by a
  * reused divisor (div_by(x, recip(y)), dfxp_device.h) differs in any bit from x / y; if qa
@@ -1148,7 +1183,7 @@ int lbt_dfxp_range_pick(const uint64_t* tables, const int32_t* slots, int32_t nj
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
  * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather,
- * lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
+ * lbt_batch_resized_crop, lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
  * earlier signature and result stands.                                                              */
 int lbt_abi_version(void);
 

@@ -341,6 +341,9 @@ _SIGS = {
     "lbt_eval_tally": [_P, _P, c_int32, c_int32, _P, _P],
     "lbt_batch_gather": [_P, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                          c_int32, c_int64, c_uint64, c_uint64, _P],
+    "lbt_batch_resized_crop": [_P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
+                               c_int32, c_int32, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P,
+                               c_int64, c_uint64, c_uint64, _P],
     "lbt_step_update": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_int32, _P, _P],
     "lbt_summary_record_bytes": [c_int32, c_int32],
     "lbt_summary_scratch_bytes": [c_int32, c_int64],

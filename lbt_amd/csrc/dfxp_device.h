@@ -134,6 +134,10 @@ LBT_DEV float u24(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-8f;
 // counter (n, kAugStream, counter_lo, counter_hi), key = seed: flip = r.x & 1, oy = r.y % (2 pad + 1),
 // ox = r.z % (2 pad + 1).
 constexpr uint32_t kAugStream = 0x41554721u;  // "AUG!"
+// RandomResizedCrop's draws (batch_input.hip): attempt t = 0..9 of sample n is the Philox call with counter
+// (n, kRrcStream + t, counter_lo, counter_hi), key = seed: area from r.x, aspect ratio from r.y >> 24,
+// top from r.z, left from r.w. The flip of the same sample stays kAugStream's r.x & 1.
+constexpr uint32_t kRrcStream = 0x52524321u;  // "RRC!"
 
 // Noise for the 4 consecutive noise indices 4*blk .. 4*blk+3 of one quantiser at one step.
 struct Noise4 { float u[4]; };

@@ -7,6 +7,11 @@ the float64 mean beside them, and ``batch()`` writes the batch a step reads with
 (``lbt_batch_gather``): gather, that normalisation, and ``preprocess_image``'s flip + crop
 (``trainer.py:24-28``) -- bit for bit what the host path feeds, with nothing crossing PCIe and nothing
 synchronising per step. ``Trainer.train()`` / ``Trainer.evaluate()`` take one in place of the arrays.
+
+A ``ResizedCropDataset`` is the same for the reference's ImageNet pipeline (``data.py:58-93``): uint8 images
+of one stored size on the device, and one ``lbt_batch_resized_crop`` launch per batch for
+``RandomResizedCrop`` + ``RandomHorizontalFlip`` (or the validation centre crop), the bilinear resample and
+``Normalize``. Both classes give the Trainer's loops ``sample_shape``, ``train_batch`` and ``test_batch``.
 """
 import numpy as np
 import torch
@@ -106,3 +111,128 @@ class DeviceDataset:
         ops.batch_gather(self._data, self._mean, self._labels, ox, out_y, idx=idx, first=first, pad=pad, flip=flip,
                          base=base, seed=seed, counter=counter)
         return out_X, out_y
+
+    # -- what the Trainer's epoch loops call, on either dataset class -------------------------
+    @property
+    def sample_shape(self):
+        """Shape of one sample of a batch."""
+        return tuple(self.shape[1:])
+
+    def train_batch(self, out_X, out_y, *, idx, augment, base=0, seed=0, counter=0):
+        """A training batch of the permutation slice idx (checked by ``upload_index``): preprocess_image's
+        flip + pad-4 crop when augmenting, a plain gather otherwise."""
+        return self.batch(out_X, out_y, idx=idx, pad=4 if augment else 0, flip=bool(augment), base=base, seed=seed,
+                          counter=counter, check=False)
+
+    def test_batch(self, out_X, out_y, *, first):
+        """Test samples [first, first + B) as they are."""
+        return self.batch(out_X, out_y, first=first)
+
+
+class ResizedCropDataset:
+    """The reference's ImageNet pipeline (``data.py:58-93``) from device memory: X [n, Hs, Ws, C] uint8 of
+    one stored size (resized offline, e.g. to 256 x 256), y [n] integer labels; ``mean`` / ``std`` per
+    channel in ``Normalize``'s units (of pixel / 255); ``size`` the output (Ho, Wo), or one int for both.
+
+    ``batch(augment=True)`` is the training transform -- ``RandomResizedCrop(size, scale, ratio)``,
+    ``RandomHorizontalFlip``, ``ToTensor``, ``Normalize`` -- and ``batch()`` the validation one: the central
+    ``center`` = (ch, cw) box (default 7/8 of the store: 224 of 256, ``Resize(256)`` + ``CenterCrop(224)`` on a
+    256 x 256 store) resampled to ``size``. One ``lbt_batch_resized_crop`` launch writes the fp32 batch; the
+    transform is defined in integers (include/lbt_dfxp.h) on the constants prepared here once: ``a_lo``,
+    ``a_hi`` (the box's area in pixels), ``ratio_q16`` (256 log-uniform aspect ratios, Q16), ``q_lo``,
+    ``q_hi``, ``shift`` and ``scale_c`` (float64 per channel). Bilinear without antialiasing: keep the store
+    near the output size."""
+
+    def __init__(self, X, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None):
+        X, y = _host(X), _host(y)
+        if X.dtype != np.uint8:
+            raise TypeError("ResizedCropDataset holds uint8 images, got %s" % X.dtype)
+        if X.ndim != 4:
+            raise ValueError("X must be [n, Hs, Ws, C], got shape %s" % (X.shape,))
+        if not np.issubdtype(y.dtype, np.integer):
+            raise TypeError("labels must be integers, got %s" % y.dtype)
+        if y.ndim != 1 or len(y) != len(X):
+            raise ValueError("X holds %d samples, y %s" % (len(X), y.shape))
+        if len(X) == 0:
+            raise ValueError("an empty dataset")
+        n, Hs, Ws, C = X.shape
+        Ho, Wo = (size, size) if isinstance(size, (int, np.integer)) else tuple(size)
+        Ho, Wo = int(Ho), int(Wo)
+        if min(Hs, Ws, C, Ho, Wo) < 1 or max(Hs, Ws, Ho, Wo) > 8192:
+            raise ValueError("stored and output sizes must lie in [1, 8192], got %dx%d -> %dx%d" % (Hs, Ws, Ho, Wo))
+        mean, std = (np.array(_host(v), dtype=np.float64).reshape(-1) for v in (mean, std))
+        if mean.shape != (C,) or std.shape != (C,):
+            raise ValueError("mean and std must hold one value per channel (%d)" % C)
+        if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std > 0)):
+            raise ValueError("mean must be finite and std positive")
+        s0, s1 = (float(v) for v in scale)
+        r0, r1 = (float(v) for v in ratio)
+        if not 0 < s0 <= s1 <= 1:
+            raise ValueError("scale must satisfy 0 < scale[0] <= scale[1] <= 1, got %s" % (scale,))
+        if not 0 < r0 <= r1:
+            raise ValueError("ratio must satisfy 0 < ratio[0] <= ratio[1], got %s" % (ratio,))
+        self.a_lo = max(1, int(np.ceil(s0 * Hs * Ws)))
+        self.a_hi = max(self.a_lo, int(np.floor(s1 * Hs * Ws)))
+        k = (np.arange(256, dtype=np.float64) + 0.5) / 256
+        self.ratio_q16 = np.rint(65536 * np.exp(np.log(r0) + k * (np.log(r1) - np.log(r0))))
+        self.q_lo, self.q_hi = int(np.rint(65536 * r0)), int(np.rint(65536 * r1))
+        if self.q_lo < 1 or self.q_hi >= 1 << 32 or self.ratio_q16.min() < 1 or self.ratio_q16.max() >= 1 << 32:
+            raise ValueError("ratio %s does not fit 16.16 fixed point" % (ratio,))
+        self.ratio_q16 = self.ratio_q16.astype(np.uint32)
+        self.shift = 65536.0 * 255.0 * mean
+        self.scale_c = 1.0 / (65536.0 * 255.0 * std)
+        if center is None:
+            center = ((7 * Hs + 4) // 8, (7 * Ws + 4) // 8)
+        self.center = (int(center[0]), int(center[1]))
+        if not (1 <= self.center[0] <= Hs and 1 <= self.center[1] <= Ws):
+            raise ValueError("the centre box %s does not fit the stored %dx%d" % (self.center, Hs, Ws))
+        self.shape = tuple(X.shape)
+        self.sample_shape = (Ho, Wo, C)
+        self.mean, self.std = mean, std
+        self.device = torch.device(device if device is not None else "cuda")
+        self._data = torch.from_numpy(np.ascontiguousarray(X)).to(self.device)
+        self._labels = torch.from_numpy(y.astype(np.int32)).to(self.device)
+        self._ratio = torch.from_numpy(self.ratio_q16.view(np.int32).copy()).to(self.device)  # the bit patterns
+        self._shift = torch.from_numpy(self.shift).to(self.device)
+        self._scale = torch.from_numpy(self.scale_c).to(self.device)
+
+    def __len__(self):
+        return self.shape[0]
+
+    upload_index = DeviceDataset.upload_index
+
+    def batch(self, out_X, out_y, *, idx=None, first=0, augment=False, base=0, seed=0, counter=0, check=True):
+        """Write one batch into out_X [B, Ho, Wo, C] fp32 / out_y [B] int32 on the current stream: sample b is
+        source sample idx[b] (a device int32 tensor of B indices) or first + b; augment: the random box and
+        flip of sample base + b of (seed, counter) -- Trainer.train() passes the context's seed and its global
+        step -- else the centre box. check as in DeviceDataset.batch."""
+        B = out_X.shape[0]
+        if tuple(out_X.shape[1:]) != self.sample_shape:
+            raise ValueError("out_X must be [B, %s], got %s" % (", ".join(map(str, self.sample_shape)), tuple(out_X.shape)))
+        for t in (out_X, out_y) + (() if idx is None else (idx,)):
+            if t.device != self._data.device:  # the kernel takes raw pointers
+                raise ValueError("the dataset lives on %s, a batch tensor on %s" % (self._data.device, t.device))
+        if idx is None:
+            if first < 0 or first + B > len(self):
+                raise IndexError("samples [%d, %d) of a dataset of %d" % (first, first + B, len(self)))
+        elif check and idx.numel():
+            lo, hi = torch.aminmax(idx)
+            if int(lo) < 0 or int(hi) >= len(self):
+                raise IndexError("idx out of range for a dataset of %d samples" % len(self))
+        ops.batch_resized_crop(self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale,
+                               a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi, center=self.center,
+                               idx=idx, first=first, augment=augment, base=base, seed=seed, counter=counter)
+        return out_X, out_y
+
+    def train_batch(self, out_X, out_y, *, idx, augment, base=0, seed=0, counter=0):
+        """A training batch of the permutation slice idx (checked by ``upload_index``): the random box and
+        flip when augmenting, the validation transform otherwise."""
+        return self.batch(out_X, out_y, idx=idx, augment=bool(augment), base=base, seed=seed, counter=counter,
+                          check=False)
+
+    def test_batch(self, out_X, out_y, *, first):
+        """Test samples [first, first + B) through the validation transform."""
+        return self.batch(out_X, out_y, first=first)
+
+
+DEVICE_DATASETS = (DeviceDataset, ResizedCropDataset)  # what Trainer.train() / evaluate() take in place of arrays

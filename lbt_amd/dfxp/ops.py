@@ -789,6 +789,39 @@ def batch_gather(data, mean, labels, out_X, out_y, idx=None, first=0, pad=0, fli
     return out_X, out_y
 
 
+def batch_resized_crop(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *, a_lo, a_hi, q_lo, q_hi, center,
+                       idx=None, first=0, augment=False, base=0, seed=0, counter=0):
+    """The ImageNet batch the step reads from a device-resident uint8 dataset (lbt_batch_resized_crop):
+    sample b of out_X [B, Ho, Wo, C] / out_y is source sample idx[b] (or first + b) of data [n, Hs, Ws, C],
+    cropped to the RandomResizedCrop box of sample base + b and flipped (augment) or to the central
+    ``center`` = (ch, cw) box, resampled bilinearly and normalised. ratio_q16 [256] int32 (the uint32 bit
+    patterns), shift / scale_c [C] float64 and the integer constants are the host-prepared ones of
+    lbt_dfxp.h (lbt_amd.data.ResizedCropDataset builds them)."""
+    _check(data, torch.uint8, "data")
+    _check(labels, torch.int32, "labels")
+    _check(out_X, torch.float32, "out_X")
+    _check(out_y, torch.int32, "out_y")
+    _check(ratio_q16, torch.int32, "ratio_q16")
+    _check(shift, torch.float64, "shift")
+    _check(scale_c, torch.float64, "scale_c")
+    n, Hs, Ws, C = data.shape
+    B, Ho, Wo = out_X.shape[:3]
+    if out_X.dim() != 4 or out_X.shape[3] != C or labels.numel() != n or out_y.numel() != B:
+        raise ValueError("batch_resized_crop: labels / out_X / out_y do not match data %s at batch %d"
+                         % (tuple(data.shape), B))
+    if ratio_q16.numel() != 256 or shift.numel() != C or scale_c.numel() != C:
+        raise ValueError("batch_resized_crop: ratio_q16 must hold 256 entries, shift and scale_c one per channel")
+    if idx is not None:
+        _check(idx, torch.int32, "idx")
+        if idx.numel() != B:
+            raise ValueError("idx must hold one source index per output sample")
+    call("lbt_batch_resized_crop", ptr(data), ptr(labels), n, ptr(idx), int(first), ptr(out_X), ptr(out_y), B, Hs, Ws,
+         C, Ho, Wo, int(bool(augment)), int(a_lo), int(a_hi), ptr(ratio_q16), int(q_lo), int(q_hi), int(center[0]),
+         int(center[1]), ptr(shift), ptr(scale_c), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
+    return out_X, out_y
+
+
 def maxpool_fwd(x, y, amax, d):
     _check(x, torch.float32, "x")
     with _Timed("maxpool_fwd_kernel", 4 * x.numel() + 5 * y.numel()):

@@ -51,7 +51,7 @@ import torch.distributed as dist
 
 from . import _lib
 from . import distributed as D
-from .data import DeviceDataset
+from .data import DEVICE_DATASETS
 from .dfxp import ops
 
 
@@ -725,7 +725,8 @@ class Trainer:
         lbt_augment_flip_crop), the lr schedule of :122-140, and the test loop after every epoch.
         Returns the per-epoch test accuracies.
         A dataset (DeviceDataset, DeviceDataset | None) (lbt_amd.data) runs the same epochs from device
-        memory: see _train_device.
+        memory: see _train_device. A pair of ResizedCropDataset runs them with the ImageNet transforms
+        (the random box and flip per training sample when augmenting, the centre crop for the test loop).
         Under a process group of ``world`` > 1 ranks (a data-parallel trainer) the epoch is sharded:
         ``batch_size`` stays the GLOBAL batch (trainer.py:34); rank 0 draws the epoch's permutation where
         the single process draws it and broadcasts it (one small collective per epoch, outside any
@@ -736,7 +737,7 @@ class Trainer:
         allocated or launched (ValueError). With FusedResNet(sync_bn=True), or a ranked context's plain
         model, N ranks leave the parameters, momentum, exponents and BN statistics of one process with
         the same torch seed, bit for bit; batch_sizes records the global nb. No timing is claimed for it."""
-        if isinstance(self.dataset[0], DeviceDataset):
+        if isinstance(self.dataset[0], DEVICE_DATASETS):
             return self._train_device(augment)
         (Xtr, ytr), (Xte, yte) = self.dataset
         self._check_epoch(len(Xtr))
@@ -775,7 +776,7 @@ class Trainer:
     def _batch_buffers(self, ds, n):
         """The fixed (X, y) pair every batch of n samples is gathered into: a model that binds its inputs
         then holds one captured graph per batch size."""
-        key = (n,) + tuple(ds.shape[1:])
+        key = (n,) + tuple(ds.sample_shape)
         if key not in self._inbuf:
             dev = self.ctx.device
             self._inbuf[key] = (torch.empty(key, dtype=torch.float32, device=dev),
@@ -789,7 +790,9 @@ class Trainer:
         lbt_augment_flip_crop makes at this step -- into the batch size's buffer pair, then the step, on
         one stream. No batch crosses PCIe and nothing synchronises inside the epoch (but the logger line
         every 100 batches). The gather is launched ahead of the step's graph, not captured into it: its
-        arguments change every step. Bit for bit the host loop on ds.host_float().
+        arguments change every step. Bit for bit the host loop on ds.host_float(). (A ResizedCropDataset:
+        the same loop with one lbt_batch_resized_crop launch per step, through the classes' common
+        train_batch / test_batch / sample_shape.)
         Sharded (see train()): every rank holds the whole dataset on its GPU and uploads the broadcast
         permutation; rank r's launch gathers idx = perm[b + r*s : b + (r+1)*s] with base = r*s into a
         buffer pair of the shard's size s = nb / world."""
@@ -812,8 +815,8 @@ class Trainer:
                 nb = min(self.batch_size, n - b)
                 lo, hi = self._shard_of(nb)  # (one process: the whole batch, base 0)
                 X, y = self._batch_buffers(ds, hi - lo)
-                ds.batch(X, y, idx=self._perm[b + lo:b + hi], pad=4 if augment else 0, flip=bool(augment), base=lo,
-                         seed=self.ctx.seed, counter=self.global_step, check=False)
+                ds.train_batch(X, y, idx=self._perm[b + lo:b + hi], augment=augment, base=lo, seed=self.ctx.seed,
+                               counter=self.global_step)
                 loss = self.step(X, y)
                 self.batch_sizes.append(nb)
                 if (b // self.batch_size + 1) % 100 == 0 and (self.logger is not None or self._sring is not None):
@@ -844,7 +847,7 @@ class Trainer:
             for b in range(0, len(ds), batch_size):
                 nb = min(batch_size, len(ds) - b)
                 Xb, yb = self._batch_buffers(ds, nb)
-                ds.batch(Xb, yb, first=b)
+                ds.test_batch(Xb, yb, first=b)
                 if not testing:
                     p, shared = self._eval_model(nb)
                 elif fused:
@@ -925,7 +928,7 @@ class Trainer:
         and element counts are saved and restored as in the other loops."""
         from .fused import FusedResNet
         m, dev, ctx = self.model, self.ctx.device, self.ctx
-        ds = X if isinstance(X, DeviceDataset) else None
+        ds = X if isinstance(X, DEVICE_DATASETS) else None
         n = len(X)
         starts = list(range(0, n, batch_size))
         if not starts:
@@ -943,7 +946,7 @@ class Trainer:
                 lo, hi = shard_rows(nb, self.world, self.rank) if split else (0, nb)
                 if ds is not None:
                     Xb, yb = self._batch_buffers(ds, hi - lo)
-                    ds.batch(Xb, yb, first=b + lo)
+                    ds.test_batch(Xb, yb, first=b + lo)
                 else:
                     Xb = torch.as_tensor(X[b + lo:b + hi], dtype=torch.float32).to(dev).contiguous()
                     yb = torch.as_tensor(y[b + lo:b + hi], dtype=torch.int32).to(dev)
@@ -1032,11 +1035,11 @@ class Trainer:
         (_unsynced): a rank's moments of the whole test batch are the one process's.
         A layer-wise model's BN statistics are added into the context's sums arena, which this trainer
         clears once per training step: the loops clear it before each test batch's forward as well."""
-        if isinstance(X, DeviceDataset) and y is not None:
+        if isinstance(X, DEVICE_DATASETS) and y is not None:
             raise TypeError("a DeviceDataset carries its labels: evaluate(ds, batch_size=..., testing=...)")
         if self._shards_eval(testing):
             return self._evaluate_sharded(X, y, batch_size, testing)
-        if isinstance(X, DeviceDataset):
+        if isinstance(X, DEVICE_DATASETS):
             with self._unsynced():  # (a layer-wise SyncBN model: every rank holds the test batch whole)
                 return self._evaluate_device(X, batch_size, testing)
         if testing:
