@@ -984,6 +984,46 @@ int lbt_batch_resized_crop(const uint8_t* data, const int32_t* labels, int64_t n
                            const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, int32_t ch, int32_t cw,
                            const double* shift, const double* scale_c, int64_t base, uint64_t seed, uint64_t counter,
                            void* stream);
+/* lbt_batch_resized_crop with torchvision's ColorJitter(brightness, contrast, saturation) between the
+ * bilinear blend and the normalisation (data.py:71-84's training transform; hue is not built). Every argument
+ * of lbt_batch_resized_crop keeps its meaning; augment == 0 ignores the jitter entirely (the validation
+ * transform: the plain launch). The jitter works on the blend's own t -- int32, units of 2^-16 pixel, in [0,
+ * T], T = 255 * 65536 -- in integers; nothing is rounded to uint8 in between (PIL rounds after the resize and
+ * after every operation: not restated). tests/color_jitter_oracle.py restates it in numpy.
+ *   factors: per operation a range [lo, hi] in Q12 the caller prepares: for a scalar v >= 0, lo = rint(4096 *
+ *     max(0, 1 - v)), hi = rint(4096 * (1 + v)); for a (min, max) pair rint(4096 * min), rint(4096 * max).
+ *   draw: r = Philox of (base + b, "CJT!" = 0x434A5421, counter; seed), keyed as "RRC!" and "AUG!" are.
+ *     order = r0 % 6 indexes the permutations of (B, C, S) in lexicographic order: BCS, BSC, CBS, CSB, SBC,
+ *     SCB. f_B = fb_lo + r1 % (fb_hi - fb_lo + 1), f_C from r2 and f_S from r3 the same way.
+ *   on a pixel's (t_R, t_G, t_B), 64-bit integers:
+ *     grey(p)        = (19595 t_R + 38470 t_G + 7471 t_B + 32768) >> 16      (PIL's "L" weights; <= T)
+ *     blend(t, d, f) = clamp(floor((4096 d + 2048 + f (t - d)) / 4096), 0, T)   (t - d signed: a floor)
+ *     brightness: d = 0; saturation: d = grey(p) of the pixel as it stands; contrast: d = M = (sum of grey(p)
+ *     + Ho Wo / 2) / (Ho Wo), the sum (uint64, <= 2^50) over the whole Ho x Wo output image as it stands when
+ *     contrast's turn comes: after the resample, the flip and the operations before contrast in this order.
+ *   X = (float)(((double)t - shift[c]) * scale_c[c]), as in the plain launch.
+ * f = 4096 returns t exactly in every operation, so all six bounds at 4096 equal lbt_batch_resized_crop bit for
+ * bit. Two launches on the stream: a statistics pass writes one uint64 sum of grey per (sample, row strip)
+ * into work, the output pass adds a sample's sums (integers: any order) and forms M. work must hold
+ * lbt_batch_resized_crop_jitter_work(B, Ho) = B * strips entries, strips = ceil(Ho / rows), rows =
+ * clamp(ceil(Ho / ceil(1024 / B)), 1, 4096): the plain launch's row strips. Every entry is written before it is
+ * read: work needs no zeroing and can be reused by the next launch on the stream. With fc_lo == fc_hi == 4096
+ * (contrast off) the statistics pass is skipped and work may be NULL. Stream-ordered, no allocation, no
+ * synchronisation: capturable. LBT_EINVAL before any HIP call: everything lbt_batch_resized_crop refuses; C
+ * != 3; a pair of bounds outside 0 <= lo <= hi <= 65536; with augment != 0 and contrast not off, work == NULL
+ * or work_len < lbt_batch_resized_crop_jitter_work(B, Ho). An idx value outside [0, n_data) reads nothing in
+ * either pass: a zero image and label -1. 16-byte stores (four pixels, three per lane) when Wo % 4 == 0 and
+ * X is 16-byte aligned, else 4-byte: the same values. (Added under ABI 24.)                              */
+int lbt_batch_resized_crop_jitter(const uint8_t* data, const int32_t* labels, int64_t n_data, const int32_t* idx,
+                                  int64_t first, float* X, int32_t* y, int32_t B, int32_t Hs, int32_t Ws, int32_t C,
+                                  int32_t Ho, int32_t Wo, int32_t augment, int64_t a_lo, int64_t a_hi,
+                                  const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, int32_t ch, int32_t cw,
+                                  const double* shift, const double* scale_c, int64_t base, uint64_t seed,
+                                  uint64_t counter, int32_t fb_lo, int32_t fb_hi, int32_t fc_lo, int32_t fc_hi,
+                                  int32_t fs_lo, int32_t fs_hi, uint64_t* work, int64_t work_len, void* stream);
+/* Entries of uint64 scratch lbt_batch_resized_crop_jitter needs for a batch of B samples of Ho rows (host only,
+ * the formula above); -1 for B <= 0 or Ho outside [1, 8192]. (Added under ABI 24.)                        */
+int64_t lbt_batch_resized_crop_jitter_work(int32_t B, int32_t Ho);
 
 /* Diagnostics: counts (atomically into *bad) the i < n where the BN kernels' division by a
  * reused divisor (div_by(x, recip(y)), dfxp_device.h) differs in any bit from x / y; if qa
@@ -1183,7 +1223,7 @@ int lbt_dfxp_range_pick(const uint64_t* tables, const int32_t* slots, int32_t nj
 /* ABI version for the Python loader: 24 (lbt_dropout_fwd / _bwd / _quantize). The testing-mode contract
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
  * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather,
- * lbt_batch_resized_crop, lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
+ * lbt_batch_resized_crop, lbt_batch_resized_crop_jitter (+ _work), lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
  * earlier signature and result stands.                                                              */
 int lbt_abi_version(void);
 

@@ -344,6 +344,11 @@ _SIGS = {
     "lbt_batch_resized_crop": [_P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                c_int32, c_int32, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P,
                                c_int64, c_uint64, c_uint64, _P],
+    "lbt_batch_resized_crop_jitter": [_P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_int32, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P,
+                                      _P, c_int64, c_uint64, c_uint64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, _P, c_int64, _P],
+    "lbt_batch_resized_crop_jitter_work": [c_int32, c_int32],
     "lbt_step_update": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_int32, _P, _P],
     "lbt_summary_record_bytes": [c_int32, c_int32],
     "lbt_summary_scratch_bytes": [c_int32, c_int64],
@@ -373,7 +378,8 @@ def load(path=LIB_PATH):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int32
-    for name in ("lbt_igemm_workspace_bytes", "lbt_summary_record_bytes", "lbt_summary_scratch_bytes"):
+    for name in ("lbt_igemm_workspace_bytes", "lbt_summary_record_bytes", "lbt_summary_scratch_bytes",
+                 "lbt_batch_resized_crop_jitter_work"):
         getattr(lib, name).restype = c_int64  # the int64-valued queries
     if lib.lbt_abi_version() != ABI_VERSION:
         raise ImportError("lbt_amd ABI mismatch: library %d, bindings %d" % (lib.lbt_abi_version(), ABI_VERSION))

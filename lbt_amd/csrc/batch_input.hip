@@ -7,6 +7,8 @@
 //                      RandomHorizontalFlip (training) or a centre crop (validation), a bilinear resample
 //                      to the output size and Normalize(mean, std), all in integers up to one float64
 //                      subtract-multiply per element (below, at its kernel)
+//   lbt_batch_resized_crop_jitter   the same with ColorJitter's brightness, contrast and saturation between the
+//                      resample and the normalisation, in integers (at the end of this file)
 //
 // lbt_batch_gather: one workgroup per output sample: the source index and the Philox draw depend on blockIdx only, so
 // they are wave-uniform. A streaming pass bound by its stores (4 B written per byte read): each lane
@@ -323,5 +325,330 @@ extern "C" int lbt_batch_resized_crop(const uint8_t* data, const int32_t* labels
     hipLaunchKernelGGL((resized_crop_kernel<true>), grid, dim3(kT), lds, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((resized_crop_kernel<false>), grid, dim3(kT), lds, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ lbt_batch_resized_crop_jitter
+// ColorJitter (brightness, contrast, saturation; lbt_dfxp.h) between the blend and the normalisation, on the
+// grid, prologue and LDS tables of resized_crop_kernel (restated here: that kernel stays as it is). Saturation
+// and grey need a pixel's three channels, so a thread owns whole pixels: four (48 contiguous, 16-byte aligned
+// bytes per lane) when Wo is a multiple of four and X is aligned, else one (12 bytes, 4-byte aligned). The order and the factors are one
+// Philox call per workgroup: wave-uniform, every branch on them is a scalar branch. Contrast needs the mean
+// grey of the whole image, which is many workgroups: jitter_stats_kernel resamples its strip, applies what
+// precedes contrast in the sample's order (jit_pixel_pre, the same function the output kernel calls) and
+// writes the strip's integer sum of grey; jitter_out_kernel adds a sample's sums in a uniform loop. Integer
+// sums: no order matters and nothing is zeroed. The stats pass repeats the loads and the blend of the output
+// pass (the box is in cache) and stores nothing.
+namespace {
+
+constexpr int32_t kJitT = 255 * 65536;  // the largest blend value
+constexpr int32_t kJitOne = 4096;       // Q12 factor 1: every operation returns t
+constexpr uint32_t kJitStream = 0x434A5421u;  // "CJT!"
+enum : uint32_t { kOpB = 0, kOpC = 1, kOpS = 2 };
+
+struct JitArgs {
+  RrcArgs r;
+  uint32_t fb_lo, fb_span, fc_lo, fc_span, fs_lo, fs_span;  // factor = lo + draw % span
+  uint64_t* work;  // [B][strips] sums of grey, or NULL with contrast off
+  uint32_t strips;
+};
+
+// A sample's draw. seq: the order's three operations, two bits each, the first in the low bits; f: the three
+// factors (<= 65536), 17 bits each, at 17 * operation -- shifts of a scalar, where three fields picked by the
+// operation became an indexed read of a stack copy.
+struct Jit {
+  uint32_t seq, cpos;  // cpos: contrast's place in the order
+  uint64_t f;
+};
+
+LBT_DEV int32_t jit_factor(const Jit& j, uint32_t op) { return (int32_t)((j.f >> (17 * op)) & 0x1FFFFu); }
+
+LBT_DEV Jit jit_draw(const JitArgs& a, uint32_t key) {
+  const U4 r = philox(key, kJitStream, (uint32_t)a.r.counter, (uint32_t)(a.r.counter >> 32), (uint32_t)a.r.seed,
+                      (uint32_t)(a.r.seed >> 32));
+  // BCS, BSC, CBS, CSB, SBC, SCB as (first | second << 2 | third << 4), six bits per order
+  constexpr uint64_t kSeq = (uint64_t)(kOpB | kOpC << 2 | kOpS << 4) | (uint64_t)(kOpB | kOpS << 2 | kOpC << 4) << 6 |
+                            (uint64_t)(kOpC | kOpB << 2 | kOpS << 4) << 12 | (uint64_t)(kOpC | kOpS << 2 | kOpB << 4) << 18 |
+                            (uint64_t)(kOpS | kOpB << 2 | kOpC << 4) << 24 | (uint64_t)(kOpS | kOpC << 2 | kOpB << 4) << 30;
+  Jit j;
+  j.seq = (uint32_t)(kSeq >> (6 * (r.x % 6u))) & 63u;
+  j.cpos = (j.seq & 3u) == kOpC ? 0u : ((j.seq >> 2) & 3u) == kOpC ? 1u : 2u;
+  j.f = (uint64_t)(a.fb_lo + r.y % a.fb_span) << (17 * kOpB) | (uint64_t)(a.fc_lo + r.z % a.fc_span) << (17 * kOpC) |
+        (uint64_t)(a.fs_lo + r.w % a.fs_span) << (17 * kOpS);
+  return j;
+}
+
+// PIL's "L" weights (they sum to 65536: grey <= kJitT); 64-bit: 38470 * 2^24 > 2^32
+LBT_DEV int32_t jit_grey(const int32_t (&t)[3]) {
+  return (int32_t)((19595ull * (uint32_t)t[0] + 38470ull * (uint32_t)t[1] + 7471ull * (uint32_t)t[2] + 32768ull) >> 16);
+}
+
+// clamp(floor((4096 d + 2048 + f (t - d)) / 4096), 0, T): f < 2^17, |t - d| < 2^25, the shift of the signed
+// sum is the floor
+LBT_DEV int32_t jit_blend(int32_t t, int32_t d, int32_t f) {
+  const int64_t v = (((int64_t)d << 12) + 2048 + (int64_t)f * (int64_t)(t - d)) >> 12;
+  return v < 0 ? 0 : v > kJitT ? kJitT : (int32_t)v;
+}
+
+// Operation k of the sample's order on one pixel (uniform branches). A factor of one is skipped: it returns t.
+LBT_DEV void jit_apply(const Jit& j, uint32_t k, int32_t M, int32_t (&t)[3]) {
+  const uint32_t op = (j.seq >> (2 * k)) & 3u;
+  const int32_t f = jit_factor(j, op);
+  if (f == kJitOne) return;
+  const int32_t d = op == kOpB ? 0 : op == kOpC ? M : jit_grey(t);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) t[c] = jit_blend(t[c], d, f);
+}
+
+// One output pixel as it stands when contrast's turn comes: the bilinear blend of its three channels
+// (resized_crop_kernel's arithmetic; x0 / x1 are the taps' byte offsets of channel 0), then the operations
+// before contrast in the sample's order. Both kernels call this.
+LBT_DEV void jit_pixel_pre(const uint8_t* __restrict__ src, uint32_t row0, uint32_t row1, int32_t fy, uint32_t x0,
+                           uint32_t x1, int32_t fx, const Jit& j, int32_t (&t)[3]) {
+  int32_t p00[3], p01[3], p10[3], p11[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p00[c] = src[row0 + x0 + c];
+    p01[c] = src[row0 + x1 + c];
+    p10[c] = src[row1 + x0 + c];
+    p11[c] = src[row1 + x1 + c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int32_t top = (256 - fx) * p00[c] + fx * p01[c];
+    const int32_t bot = (256 - fx) * p10[c] + fx * p11[c];
+    t[c] = (int32_t)(__umul24(256 - fy, top) + __umul24(fy, bot));  // factors < 2^24; <= 255 * 65536
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 2; ++k)
+    if (k < j.cpos) jit_apply(j, k, 0, t);
+}
+
+// What every strip of a sample resolves first, as resized_crop_kernel does: source sample, box, flip and the
+// tap tables in LDS; here also the jitter's draw. Ends in the barrier that publishes the tables.
+struct JitStrip {
+  uint32_t i0, nrow;
+  bool ok;
+  const uint8_t* src;
+  Jit j;
+};
+
+LBT_DEV JitStrip jit_prologue(const JitArgs& ja, uint32_t* tab, bool write_label) {
+  const RrcArgs& a = ja.r;
+  JitStrip s;
+  const uint32_t b = blockIdx.x;
+  s.i0 = blockIdx.y * a.rows;
+  s.nrow = a.Ho - s.i0 < a.rows ? a.Ho - s.i0 : a.rows;
+  const int64_t sm = a.idx ? (int64_t)a.idx[b] : a.first + (int64_t)b;
+  s.ok = sm >= 0 && sm < a.n_data;
+  const uint32_t key = (uint32_t)(a.base + (int64_t)b);
+  const Box box = rrc_box(a, key);
+  const bool fl = a.augment && (philox(key, kAugStream, (uint32_t)a.counter, (uint32_t)(a.counter >> 32),
+                                       (uint32_t)a.seed, (uint32_t)(a.seed >> 32)).x & 1u);
+  s.j = jit_draw(ja, key);
+  for (uint32_t j = threadIdx.x; j < a.Wo; j += kT) tab[j] = rrc_tap(fl ? a.Wo - 1 - j : j, box.w, a.Wo);
+  for (uint32_t i = threadIdx.x; i < s.nrow; i += kT) tab[a.Wo + i] = rrc_tap(s.i0 + i, box.h, a.Ho);
+  if (write_label && blockIdx.y == 0 && threadIdx.x == 0) a.y[b] = s.ok ? a.labels[sm] : -1;
+  __syncthreads();
+  s.src = a.data + (s.ok ? sm * (int64_t)a.Hs * a.Ws * 3 : 0) + ((int64_t)box.top * a.Ws + box.left) * 3;
+  return s;
+}
+
+// The strip's sum of grey over the pixels as they stand before contrast -> work[sample][strip]. kP as in
+// jitter_out_kernel: the same threads take the same pixels.
+template <uint32_t kP>
+__global__ __launch_bounds__(kT) void jitter_stats_kernel(const JitArgs ja) {
+  extern __shared__ uint32_t tab[];  // [Wo] column taps, [rows] this strip's row taps
+  __shared__ long long red[kT / 64];
+  const RrcArgs& a = ja.r;
+  const JitStrip s = jit_prologue(ja, tab, false);
+  const uint32_t rs = a.Ws * 3;
+  const uint32_t Q = a.Wo / kP, Qc = Q < (uint32_t)kT ? Q : (uint32_t)kT, G = (uint32_t)kT / Qc;
+  const uint32_t g = threadIdx.x / Qc, q0 = threadIdx.x - g * Qc;
+  uint64_t sum = 0;  // <= rows * Wo * kJitT < 2^50
+  if (s.ok && g < G) {  // (ok is uniform) an index outside the dataset reads nothing: its sums are zero
+    for (uint32_t q = q0; q < Q; q += Qc) {
+      uint32_t x0[kP], x1[kP];
+      int32_t fx[kP];
+#pragma unroll
+      for (uint32_t k = 0; k < kP; ++k) {
+        const uint32_t tx = tab[q * kP + k];
+        x0[k] = (tx & 8191u) * 3;
+        x1[k] = x0[k] + (tx >> 22) * 3;
+        fx[k] = (int32_t)((tx >> 13) & 511u);
+      }
+      for (uint32_t il = g; il < s.nrow; il += G) {
+        const uint32_t ty = tab[a.Wo + il];
+        const uint32_t row0 = (ty & 8191u) * rs, row1 = row0 + (ty >> 22) * rs;
+        const int32_t fy = (int32_t)((ty >> 13) & 511u);
+#pragma unroll
+        for (uint32_t k = 0; k < kP; ++k) {
+          int32_t t[3];
+          jit_pixel_pre(s.src, row0, row1, fy, x0[k], x1[k], fx[k], s.j, t);
+          sum += (uint32_t)jit_grey(t);
+        }
+      }
+    }
+  }
+  const long long w = wave_sum_i64((long long)sum);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long total = 0;
+#pragma unroll
+    for (int i = 0; i < kT / 64; ++i) total += red[i];
+    ja.work[(int64_t)blockIdx.x * ja.strips + blockIdx.y] = (uint64_t)total;
+  }
+}
+
+// resized_crop_kernel with the jitter between the blend and the normalisation. kP pixels per thread: 4 (Wo % 4
+// == 0: the twelve floats stay inside the row, 16-byte aligned with X; written as three float4, which the
+// compiler is free to regroup), or 1.
+template <uint32_t kP>
+__global__ __launch_bounds__(kT) void jitter_out_kernel(const JitArgs ja) {
+  extern __shared__ uint32_t tab[];
+  const RrcArgs& a = ja.r;
+  const JitStrip s = jit_prologue(ja, tab, true);
+  const uint32_t WoC = a.Wo * 3, rs = a.Ws * 3, total = s.nrow * WoC;  // < 2^31 (host checks)
+  float* __restrict__ out = a.X + ((int64_t)blockIdx.x * a.Ho + s.i0) * (int64_t)WoC;
+  if (!s.ok) {  // (uniform) nothing to read: a zero image
+    constexpr uint32_t kV = kP == 4 ? 4u : 1u;
+    for (uint32_t e = threadIdx.x * kV; e < total; e += kT * kV) {
+      if constexpr (kP == 4) {
+        *reinterpret_cast<float4*>(out + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        out[e] = 0.f;
+      }
+    }
+    return;
+  }
+  int32_t M = 0;  // the image's mean grey before contrast, from every strip's sum
+  if (ja.work && jit_factor(s.j, kOpC) != kJitOne) {
+    uint64_t sum = 0;
+    const uint64_t* __restrict__ part = ja.work + (int64_t)blockIdx.x * ja.strips;
+    for (uint32_t k = 0; k < ja.strips; ++k) sum += part[k];
+    const uint64_t npx = (uint64_t)a.Ho * a.Wo;
+    M = (int32_t)((sum + npx / 2) / npx);
+  }
+  const double sh0 = a.shift[0], sh1 = a.shift[1], sh2 = a.shift[2];
+  const double sc0 = a.scale[0], sc1 = a.scale[1], sc2 = a.scale[2];
+  const uint32_t Q = a.Wo / kP, Qc = Q < (uint32_t)kT ? Q : (uint32_t)kT, G = (uint32_t)kT / Qc;
+  const uint32_t g = threadIdx.x / Qc, q0 = threadIdx.x - g * Qc;
+  if (g >= G) return;
+  for (uint32_t q = q0; q < Q; q += Qc) {
+    uint32_t x0[kP], x1[kP];
+    int32_t fx[kP];
+#pragma unroll
+    for (uint32_t k = 0; k < kP; ++k) {
+      const uint32_t tx = tab[q * kP + k];
+      x0[k] = (tx & 8191u) * 3;
+      x1[k] = x0[k] + (tx >> 22) * 3;
+      fx[k] = (int32_t)((tx >> 13) & 511u);
+    }
+    for (uint32_t il = g; il < s.nrow; il += G) {
+      const uint32_t ty = tab[a.Wo + il];
+      const uint32_t row0 = (ty & 8191u) * rs, row1 = row0 + (ty >> 22) * rs;
+      const int32_t fy = (int32_t)((ty >> 13) & 511u);
+      float v[3 * kP];
+#pragma unroll
+      for (uint32_t k = 0; k < kP; ++k) {
+        int32_t t[3];
+        jit_pixel_pre(s.src, row0, row1, fy, x0[k], x1[k], fx[k], s.j, t);
+#pragma unroll
+        for (uint32_t o = 0; o < 3; ++o)
+          if (o >= s.j.cpos) jit_apply(s.j, o, M, t);
+        v[3 * k + 0] = (float)(((double)t[0] - sh0) * sc0);
+        v[3 * k + 1] = (float)(((double)t[1] - sh1) * sc1);
+        v[3 * k + 2] = (float)(((double)t[2] - sh2) * sc2);
+      }
+      float* __restrict__ o = out + il * WoC + q * (3 * kP);
+      if constexpr (kP == 4) {
+        float4* __restrict__ o4 = reinterpret_cast<float4*>(o);
+        o4[0] = make_float4(v[0], v[1], v[2], v[3]);
+        o4[1] = make_float4(v[4], v[5], v[6], v[7]);
+        o4[2] = make_float4(v[8], v[9], v[10], v[11]);
+      } else {
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+      }
+    }
+  }
+}
+
+// rows of a strip: lbt_batch_resized_crop's policy (about 1024 workgroups), which the scratch size follows
+int32_t jitter_strip_rows(int32_t B, int32_t Ho) {
+  const int32_t want = (1024 + B - 1) / B;
+  const int32_t rows = (Ho + want - 1) / want;
+  return rows < 1 ? 1 : rows > kRrcMaxRows ? kRrcMaxRows : rows;
+}
+
+bool jitter_range_ok(int32_t lo, int32_t hi) { return 0 <= lo && lo <= hi && hi <= 65536; }
+
+}  // namespace
+
+extern "C" int64_t lbt_batch_resized_crop_jitter_work(int32_t B, int32_t Ho) {
+  if (B <= 0 || Ho <= 0 || Ho > 8192) return -1;
+  const int32_t rows = jitter_strip_rows(B, Ho);
+  return (int64_t)B * ((Ho + rows - 1) / rows);
+}
+
+extern "C" int lbt_batch_resized_crop_jitter(const uint8_t* data, const int32_t* labels, int64_t n_data,
+                                             const int32_t* idx, int64_t first, float* X, int32_t* y, int32_t B,
+                                             int32_t Hs, int32_t Ws, int32_t C, int32_t Ho, int32_t Wo, int32_t augment,
+                                             int64_t a_lo, int64_t a_hi, const uint32_t* ratio_q16, int64_t q_lo,
+                                             int64_t q_hi, int32_t ch, int32_t cw, const double* shift,
+                                             const double* scale_c, int64_t base, uint64_t seed, uint64_t counter,
+                                             int32_t fb_lo, int32_t fb_hi, int32_t fc_lo, int32_t fc_hi, int32_t fs_lo,
+                                             int32_t fs_hi, uint64_t* work, int64_t work_len, void* stream) {
+  if (C != 3) return LBT_EINVAL;
+  if (!jitter_range_ok(fb_lo, fb_hi) || !jitter_range_ok(fc_lo, fc_hi) || !jitter_range_ok(fs_lo, fs_hi))
+    return LBT_EINVAL;
+  const bool stats = augment != 0 && !(fc_lo == kJitOne && fc_hi == kJitOne);
+  if (stats && (B <= 0 || Ho <= 0 || Ho > 8192 || !work || work_len < lbt_batch_resized_crop_jitter_work(B, Ho)))
+    return LBT_EINVAL;
+  if (!augment)  // the validation transform: no jitter, the plain launch (which makes every other check)
+    return lbt_batch_resized_crop(data, labels, n_data, idx, first, X, y, B, Hs, Ws, C, Ho, Wo, augment, a_lo, a_hi,
+                                  ratio_q16, q_lo, q_hi, ch, cw, shift, scale_c, base, seed, counter, stream);
+  if (!data || !labels || !X || !y || !ratio_q16 || !shift || !scale_c) return LBT_EINVAL;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 || n_data <= 0) return LBT_EINVAL;
+  if (Hs > 8192 || Ws > 8192 || Ho > 8192 || Wo > 8192) return LBT_EINVAL;
+  if ((int64_t)Hs * Ws * C >= ((int64_t)1 << 31) || (int64_t)Ho * Wo * C >= ((int64_t)1 << 31)) return LBT_EINVAL;
+  if (a_lo < 1 || a_hi < a_lo || a_hi > (int64_t)Hs * Ws) return LBT_EINVAL;
+  if (q_lo < 1 || q_hi < q_lo || q_hi > 0xFFFFFFFFLL) return LBT_EINVAL;
+  if (ch < 1 || ch > Hs || cw < 1 || cw > Ws) return LBT_EINVAL;
+  if (base < 0 || base > ((int64_t)1 << 32) - B) return LBT_EINVAL;  // the draw's key is 32 bits wide
+  if (!idx && (first < 0 || first > n_data - B)) return LBT_EINVAL;
+  const int32_t rows = jitter_strip_rows(B, Ho);
+  const int32_t strips = (Ho + rows - 1) / rows;
+  JitArgs ja;
+  RrcArgs& a = ja.r;
+  a.data = data; a.labels = labels; a.n_data = n_data; a.idx = idx; a.first = first; a.X = X; a.y = y;
+  a.Hs = (uint32_t)Hs; a.Ws = (uint32_t)Ws; a.C = 3; a.Ho = (uint32_t)Ho; a.Wo = (uint32_t)Wo;
+  a.rows = (uint32_t)rows; a.augment = 1;
+  a.a_lo = (uint32_t)a_lo; a.a_span = (uint32_t)(a_hi - a_lo + 1);
+  a.ratio = ratio_q16; a.q_lo = (uint32_t)q_lo; a.q_hi = (uint32_t)q_hi; a.ch = (uint32_t)ch; a.cw = (uint32_t)cw;
+  a.shift = shift; a.scale = scale_c; a.base = base; a.seed = seed; a.counter = counter;
+  ja.fb_lo = (uint32_t)fb_lo; ja.fb_span = (uint32_t)(fb_hi - fb_lo + 1);
+  ja.fc_lo = (uint32_t)fc_lo; ja.fc_span = (uint32_t)(fc_hi - fc_lo + 1);
+  ja.fs_lo = (uint32_t)fs_lo; ja.fs_span = (uint32_t)(fs_hi - fs_lo + 1);
+  ja.work = stats ? work : nullptr;
+  ja.strips = (uint32_t)strips;
+  const bool vec = Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  const dim3 grid((unsigned)B, (unsigned)strips);
+  const size_t lds = sizeof(uint32_t) * (size_t)(Wo + rows);
+  hipStream_t st = (hipStream_t)stream;
+  if (stats) {
+    if (vec)
+      hipLaunchKernelGGL((jitter_stats_kernel<4>), grid, dim3(kT), lds, st, ja);
+    else
+      hipLaunchKernelGGL((jitter_stats_kernel<1>), grid, dim3(kT), lds, st, ja);
+    const int e = (int)hipGetLastError();
+    if (e) return e;
+  }
+  if (vec)
+    hipLaunchKernelGGL((jitter_out_kernel<4>), grid, dim3(kT), lds, st, ja);
+  else
+    hipLaunchKernelGGL((jitter_out_kernel<1>), grid, dim3(kT), lds, st, ja);
   return (int)hipGetLastError();
 }

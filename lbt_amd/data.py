@@ -11,7 +11,8 @@ synchronising per step. ``Trainer.train()`` / ``Trainer.evaluate()`` take one in
 A ``ResizedCropDataset`` is the same for the reference's ImageNet pipeline (``data.py:58-93``): uint8 images
 of one stored size on the device, and one ``lbt_batch_resized_crop`` launch per batch for
 ``RandomResizedCrop`` + ``RandomHorizontalFlip`` (or the validation centre crop), the bilinear resample and
-``Normalize``. Both classes give the Trainer's loops ``sample_shape``, ``train_batch`` and ``test_batch``.
+``Normalize``; with ``color_jitter`` the training launch (``lbt_batch_resized_crop_jitter``) also applies
+``ColorJitter``'s brightness, contrast and saturation. Both classes give the Trainer's loops ``sample_shape``, ``train_batch`` and ``test_batch``.
 """
 import numpy as np
 import torch
@@ -129,6 +130,23 @@ class DeviceDataset:
         return self.batch(out_X, out_y, first=first)
 
 
+def _jitter_range(v, name):
+    """torchvision's ColorJitter argument -- a scalar v >= 0 for [max(0, 1 - v), 1 + v], or a (min, max) pair
+    -- as the factor range (lo, hi) in Q12."""
+    if np.ndim(v) == 0:
+        v = float(v)
+        if not v >= 0:
+            raise ValueError("%s must be non-negative, got %s" % (name, v))
+        lo, hi = max(0.0, 1.0 - v), 1.0 + v
+    else:
+        if len(v) != 2:
+            raise ValueError("%s must be a scalar or a (min, max) pair, got %s" % (name, v))
+        lo, hi = float(v[0]), float(v[1])
+    if not 0 <= lo <= hi <= 16:
+        raise ValueError("%s: the factor range must satisfy 0 <= min <= max <= 16, got (%s, %s)" % (name, lo, hi))
+    return int(np.rint(4096 * lo)), int(np.rint(4096 * hi))
+
+
 class ResizedCropDataset:
     """The reference's ImageNet pipeline (``data.py:58-93``) from device memory: X [n, Hs, Ws, C] uint8 of
     one stored size (resized offline, e.g. to 256 x 256), y [n] integer labels; ``mean`` / ``std`` per
@@ -141,9 +159,17 @@ class ResizedCropDataset:
     transform is defined in integers (include/lbt_dfxp.h) on the constants prepared here once: ``a_lo``,
     ``a_hi`` (the box's area in pixels), ``ratio_q16`` (256 log-uniform aspect ratios, Q16), ``q_lo``,
     ``q_hi``, ``shift`` and ``scale_c`` (float64 per channel). Bilinear without antialiasing: keep the store
-    near the output size."""
+    near the output size.
 
-    def __init__(self, X, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None):
+    ``color_jitter`` = (brightness, contrast, saturation), each a scalar or a (min, max) pair with
+    torchvision's meaning, adds ``ColorJitter`` to the training transform (three-channel stores; hue is not
+    built: a fourth entry must be zero): ``batch(augment=True)`` then launches
+    ``lbt_batch_resized_crop_jitter``, which draws each sample's order and factors from the Q12 ranges
+    ``fb_lo`` .. ``fs_hi`` (``jitter`` holds all six) and works in integers on the resampled pixel. ``batch()``
+    and ``test_batch`` never jitter. None: the launch is ``lbt_batch_resized_crop``."""
+
+    def __init__(self, X, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None,
+                 color_jitter=None):
         X, y = _host(X), _host(y)
         if X.dtype != np.uint8:
             raise TypeError("ResizedCropDataset holds uint8 images, got %s" % X.dtype)
@@ -186,6 +212,19 @@ class ResizedCropDataset:
         self.center = (int(center[0]), int(center[1]))
         if not (1 <= self.center[0] <= Hs and 1 <= self.center[1] <= Ws):
             raise ValueError("the centre box %s does not fit the stored %dx%d" % (self.center, Hs, Ws))
+        self.jitter = None
+        if color_jitter is not None:
+            cj = tuple(color_jitter)
+            if len(cj) not in (3, 4):
+                raise ValueError("color_jitter must be (brightness, contrast, saturation), got %s" % (color_jitter,))
+            if len(cj) == 4 and np.any(np.asarray(cj[3], dtype=np.float64) != 0):
+                raise ValueError("hue jitter is not built: color_jitter's hue must be 0, got %s" % (cj[3],))
+            if C != 3:
+                raise ValueError("color_jitter needs a three-channel store, got %d channels" % C)
+            (self.fb_lo, self.fb_hi), (self.fc_lo, self.fc_hi), (self.fs_lo, self.fs_hi) = (
+                _jitter_range(v, name) for v, name in zip(cj, ("brightness", "contrast", "saturation")))
+            self.jitter = (self.fb_lo, self.fb_hi, self.fc_lo, self.fc_hi, self.fs_lo, self.fs_hi)
+        self._work = {}  # batch size -> the contrast pass's scratch, allocated at first use and kept
         self.shape = tuple(X.shape)
         self.sample_shape = (Ho, Wo, C)
         self.mean, self.std = mean, std
@@ -205,7 +244,8 @@ class ResizedCropDataset:
         """Write one batch into out_X [B, Ho, Wo, C] fp32 / out_y [B] int32 on the current stream: sample b is
         source sample idx[b] (a device int32 tensor of B indices) or first + b; augment: the random box and
         flip of sample base + b of (seed, counter) -- Trainer.train() passes the context's seed and its global
-        step -- else the centre box. check as in DeviceDataset.batch."""
+        step -- else the centre box. With ``color_jitter``, augment also draws that sample's jitter. check as in
+        DeviceDataset.batch."""
         B = out_X.shape[0]
         if tuple(out_X.shape[1:]) != self.sample_shape:
             raise ValueError("out_X must be [B, %s], got %s" % (", ".join(map(str, self.sample_shape)), tuple(out_X.shape)))
@@ -219,10 +259,26 @@ class ResizedCropDataset:
             lo, hi = torch.aminmax(idx)
             if int(lo) < 0 or int(hi) >= len(self):
                 raise IndexError("idx out of range for a dataset of %d samples" % len(self))
+        if augment and self.jitter is not None:
+            ops.batch_resized_crop_jitter(self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale,
+                                          a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi,
+                                          center=self.center, jitter=self.jitter, work=self._jitter_work(B), idx=idx,
+                                          first=first, augment=True, base=base, seed=seed, counter=counter)
+            return out_X, out_y
         ops.batch_resized_crop(self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale,
                                a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi, center=self.center,
                                idx=idx, first=first, augment=augment, base=base, seed=seed, counter=counter)
         return out_X, out_y
+
+    def _jitter_work(self, B):
+        """The contrast pass's scratch for batches of B (None with contrast off). One buffer per batch size,
+        kept: launches on one stream reuse it in order, and a captured launch keeps its address."""
+        if (self.fc_lo, self.fc_hi) == (4096, 4096):
+            return None
+        if B not in self._work:
+            n = ops.batch_resized_crop_jitter_work(B, self.sample_shape[0])
+            self._work[B] = torch.empty(n, dtype=torch.int64, device=self._data.device)
+        return self._work[B]
 
     def train_batch(self, out_X, out_y, *, idx, augment, base=0, seed=0, counter=0):
         """A training batch of the permutation slice idx (checked by ``upload_index``): the random box and

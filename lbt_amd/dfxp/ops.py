@@ -789,14 +789,9 @@ def batch_gather(data, mean, labels, out_X, out_y, idx=None, first=0, pad=0, fli
     return out_X, out_y
 
 
-def batch_resized_crop(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *, a_lo, a_hi, q_lo, q_hi, center,
-                       idx=None, first=0, augment=False, base=0, seed=0, counter=0):
-    """The ImageNet batch the step reads from a device-resident uint8 dataset (lbt_batch_resized_crop):
-    sample b of out_X [B, Ho, Wo, C] / out_y is source sample idx[b] (or first + b) of data [n, Hs, Ws, C],
-    cropped to the RandomResizedCrop box of sample base + b and flipped (augment) or to the central
-    ``center`` = (ch, cw) box, resampled bilinearly and normalised. ratio_q16 [256] int32 (the uint32 bit
-    patterns), shift / scale_c [C] float64 and the integer constants are the host-prepared ones of
-    lbt_dfxp.h (lbt_amd.data.ResizedCropDataset builds them)."""
+def _resized_crop_shapes(name, data, labels, out_X, out_y, ratio_q16, shift, scale_c, idx):
+    """The dtype / device / shape checks of batch_resized_crop and batch_resized_crop_jitter: (n, Hs, Ws, C, B, Ho,
+    Wo)."""
     _check(data, torch.uint8, "data")
     _check(labels, torch.int32, "labels")
     _check(out_X, torch.float32, "out_X")
@@ -807,18 +802,67 @@ def batch_resized_crop(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *,
     n, Hs, Ws, C = data.shape
     B, Ho, Wo = out_X.shape[:3]
     if out_X.dim() != 4 or out_X.shape[3] != C or labels.numel() != n or out_y.numel() != B:
-        raise ValueError("batch_resized_crop: labels / out_X / out_y do not match data %s at batch %d"
-                         % (tuple(data.shape), B))
+        raise ValueError("%s: labels / out_X / out_y do not match data %s at batch %d" % (name, tuple(data.shape), B))
     if ratio_q16.numel() != 256 or shift.numel() != C or scale_c.numel() != C:
-        raise ValueError("batch_resized_crop: ratio_q16 must hold 256 entries, shift and scale_c one per channel")
+        raise ValueError("%s: ratio_q16 must hold 256 entries, shift and scale_c one per channel" % name)
     if idx is not None:
         _check(idx, torch.int32, "idx")
         if idx.numel() != B:
             raise ValueError("idx must hold one source index per output sample")
+    return n, Hs, Ws, C, B, Ho, Wo
+
+
+def batch_resized_crop(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *, a_lo, a_hi, q_lo, q_hi, center,
+                       idx=None, first=0, augment=False, base=0, seed=0, counter=0):
+    """The ImageNet batch the step reads from a device-resident uint8 dataset (lbt_batch_resized_crop):
+    sample b of out_X [B, Ho, Wo, C] / out_y is source sample idx[b] (or first + b) of data [n, Hs, Ws, C],
+    cropped to the RandomResizedCrop box of sample base + b and flipped (augment) or to the central
+    ``center`` = (ch, cw) box, resampled bilinearly and normalised. ratio_q16 [256] int32 (the uint32 bit
+    patterns), shift / scale_c [C] float64 and the integer constants are the host-prepared ones of
+    lbt_dfxp.h (lbt_amd.data.ResizedCropDataset builds them)."""
+    n, Hs, Ws, C, B, Ho, Wo = _resized_crop_shapes("batch_resized_crop", data, labels, out_X, out_y, ratio_q16, shift,
+                                                   scale_c, idx)
     call("lbt_batch_resized_crop", ptr(data), ptr(labels), n, ptr(idx), int(first), ptr(out_X), ptr(out_y), B, Hs, Ws,
          C, Ho, Wo, int(bool(augment)), int(a_lo), int(a_hi), ptr(ratio_q16), int(q_lo), int(q_hi), int(center[0]),
          int(center[1]), ptr(shift), ptr(scale_c), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF,
          int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
+    return out_X, out_y
+
+
+def batch_resized_crop_jitter_work(B, Ho):
+    """Entries of int64 scratch batch_resized_crop_jitter needs for B samples of Ho rows (one per sample and
+    row strip of the launch)."""
+    n = int(_lib.load().lbt_batch_resized_crop_jitter_work(int(B), int(Ho)))
+    if n < 0:
+        raise ValueError("batch_resized_crop_jitter_work: B = %d, Ho = %d" % (B, Ho))
+    return n
+
+
+def batch_resized_crop_jitter(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *, a_lo, a_hi, q_lo, q_hi, center,
+                              jitter, work=None, idx=None, first=0, augment=False, base=0, seed=0, counter=0):
+    """batch_resized_crop with ColorJitter's brightness, contrast and saturation between the resample and the
+    normalisation (lbt_batch_resized_crop_jitter; three channels). jitter: the six Q12 bounds (fb_lo, fb_hi,
+    fc_lo, fc_hi, fs_lo, fs_hi); sample base + b draws its order and factors. work: int64 device scratch of
+    batch_resized_crop_jitter_work(B, Ho) entries for the contrast mean (written before it is read, reusable);
+    None only with contrast off (fc_lo == fc_hi == 4096). augment=False ignores the jitter."""
+    n, Hs, Ws, C, B, Ho, Wo = _resized_crop_shapes("batch_resized_crop_jitter", data, labels, out_X, out_y, ratio_q16,
+                                                   shift, scale_c, idx)
+    if C != 3:
+        raise ValueError("batch_resized_crop_jitter: colour jitter needs three channels, data has %d" % C)
+    jitter = tuple(int(v) for v in jitter)
+    if len(jitter) != 6 or any(not 0 <= lo <= hi <= 65536 for lo, hi in zip(jitter[::2], jitter[1::2])):
+        raise ValueError("batch_resized_crop_jitter: six Q12 bounds with 0 <= lo <= hi <= 65536, got %s" % (jitter,))
+    work_len = 0
+    if work is not None:
+        _check(work, torch.int64, "work")
+        work_len = work.numel()
+    if augment and jitter[2:4] != (4096, 4096) and work_len < batch_resized_crop_jitter_work(B, Ho):
+        raise ValueError("batch_resized_crop_jitter: work must hold %d entries, got %d"
+                         % (batch_resized_crop_jitter_work(B, Ho), work_len))
+    call("lbt_batch_resized_crop_jitter", ptr(data), ptr(labels), n, ptr(idx), int(first), ptr(out_X), ptr(out_y), B,
+         Hs, Ws, C, Ho, Wo, int(bool(augment)), int(a_lo), int(a_hi), ptr(ratio_q16), int(q_lo), int(q_hi),
+         int(center[0]), int(center[1]), ptr(shift), ptr(scale_c), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(counter) & 0xFFFFFFFFFFFFFFFF, *jitter, ptr(work), work_len, stream())
     return out_X, out_y
 
 

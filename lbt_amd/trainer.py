@@ -791,7 +791,7 @@ class Trainer:
         one stream. No batch crosses PCIe and nothing synchronises inside the epoch (but the logger line
         every 100 batches). The gather is launched ahead of the step's graph, not captured into it: its
         arguments change every step. Bit for bit the host loop on ds.host_float(). (A ResizedCropDataset:
-        the same loop with one lbt_batch_resized_crop launch per step, through the classes' common
+        the same loop with one lbt_batch_resized_crop (or, with color_jitter, _jitter) launch per step, through the classes' common
         train_batch / test_batch / sample_shape.)
         Sharded (see train()): every rank holds the whole dataset on its GPU and uploads the broadcast
         permutation; rank r's launch gathers idx = perm[b + r*s : b + (r+1)*s] with base = r*s into a

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Time the ImageNet input launch (``lbt_batch_resized_crop``, lbt_amd/data.py) against a plain copy of
-its output and against the step it feeds, in one process on one GPU.
+"""Time the ImageNet input launch (``lbt_batch_resized_crop`` and, with colour jitter,
+``lbt_batch_resized_crop_jitter``; lbt_amd/data.py) against a plain copy of its output and against the step it
+feeds, in one process on one GPU.
 
     python tools/input_probe.py [--samples 1024] [--reps 20] [--iters 30] [--step-iters 10] [--no-step]
                                 [--out profiles/input/resized_crop.json]
@@ -12,7 +13,10 @@ one HIP graph, so that the host's share of a launch (argument checks, ctypes) is
 warm-up replays, ``--iters`` replays are timed with device events, and the time per launch is a replay's
 over ``--reps``; the median and the fastest are reported. The yardstick is ``copy_`` of as many fp32 bytes
 as the launch writes, timed the same way: the launch stores what the copy stores and reads a quarter of
-the bytes or fewer, so the ratio is what the resampling costs. Then
+the bytes or fewer, so the ratio is what the resampling costs. Beside the training arm, in the same form: the
+training transform with ``ColorJitter(0.4, 0.4, 0.4)`` (``jitter``: the statistics pass and the output pass) and
+with contrast off (``jitter_no_contrast``: the output pass alone), each also as a ratio to the training arm of
+this run. Then
 ``ImageNet_Resnet50`` at B = 256 (bench.py's ResNet-50 workload) is captured and ``--step-iters`` steps are
 timed, for the launch's share of a step. One JSON document, printed and written to ``--out``.
 """
@@ -81,8 +85,11 @@ def main():
     y = rng.integers(0, 1000, size=args.samples).astype(np.int32)
     ds = ResizedCropDataset(X, y, MEAN, STD, 224, device=device)
     perm = ds.upload_index(torch.from_numpy(rng.permutation(args.samples)))
+    arms = {"train": ds, "validation": ds}  # arm -> its dataset (the jitter arms hold the store again)
+    for name, cj in (("jitter", (0.4, 0.4, 0.4)), ("jitter_no_contrast", (0.4, 0.0, 0.4))):
+        arms[name] = ResizedCropDataset(X, y, MEAN, STD, 224, device=device, color_jitter=cj)
 
-    out = {"summary": "lbt_batch_resized_crop, 256x256x3 uint8 store -> 224x224x3 fp32", "samples": args.samples,
+    out = {"summary": "lbt_batch_resized_crop (+ _jitter), 256x256x3 uint8 store -> 224x224x3 fp32", "samples": args.samples,
            "launches_per_graph": args.reps, "device": torch.cuda.get_device_name(0), "launch": {}}
     for B in (256, 32):
         oX = torch.empty((B,) + ds.sample_shape, dtype=torch.float32, device=device)
@@ -90,17 +97,19 @@ def main():
         src = torch.empty_like(oX).normal_()
         slots = args.samples // B
 
-        def launch(i, augment):
+        def launch(i, arm):
             lo = (i % slots) * B
-            ds.batch(oX, oy, idx=perm[lo:lo + B], augment=augment, seed=1, counter=i, check=False)
+            arms[arm].batch(oX, oy, idx=perm[lo:lo + B], augment=arm != "validation", seed=1, counter=i, check=False)
 
         row = {"output_bytes": oX.numel() * 4}
-        row["train"] = stats(timed_graph(lambda i: launch(i, True), args.reps, args.iters))
-        row["validation"] = stats(timed_graph(lambda i: launch(i, False), args.reps, args.iters))
+        for arm in arms:
+            row[arm] = stats(timed_graph(lambda i: launch(i, arm), args.reps, args.iters))
         row["copy"] = stats(timed_graph(lambda i: oX.copy_(src), args.reps, args.iters))
-        for mode in ("train", "validation"):
+        for mode in arms:
             row[mode]["ratio_to_copy"] = round(row[mode]["median_us"] / row["copy"]["median_us"], 3)
             row[mode]["output_GBps"] = round(row["output_bytes"] / row[mode]["median_us"] / 1000, 1)
+        for mode in ("jitter", "jitter_no_contrast"):
+            row[mode]["ratio_to_train"] = round(row[mode]["median_us"] / row["train"]["median_us"], 3)
         out["launch"]["B%d" % B] = row
         del oX, src
 
@@ -121,6 +130,9 @@ def main():
         out["step"] = {"workload": "ImageNet_Resnet50, B = 256, captured", **step}
         t = out["launch"]["B256"]["train"]["median_us"]
         out["step"]["input_share_of_step"] = round(t / (step["median_us"] + t), 5)
+        for mode in ("jitter", "jitter_no_contrast"):
+            t = out["launch"]["B256"][mode]["median_us"]
+            out["step"][mode + "_share_of_step"] = round(t / (step["median_us"] + t), 5)
 
     text = json.dumps(out, indent=1)
     print(text, flush=True)
