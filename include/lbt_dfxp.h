@@ -1025,6 +1025,58 @@ int lbt_batch_resized_crop_jitter(const uint8_t* data, const int32_t* labels, in
  * the formula above); -1 for B <= 0 or Ho outside [1, 8192]. (Added under ABI 24.)                        */
 int64_t lbt_batch_resized_crop_jitter_work(int32_t B, int32_t Ho);
 
+/* One image of a ragged store: images of differing size packed into one byte array (the reference's
+ * pipeline never squashes an image: RandomResizedCrop draws inside each image's own H x W, validation is
+ * Resize(256) of the short side + CenterCrop(224); data.py:58-93). 32 bytes, no padding.                */
+typedef struct lbt_image_geom {
+  int64_t offset;      /* bytes from `data` to the image's first pixel; images are [Hs][Ws][C] uint8, dense */
+  int32_t Hs, Ws;      /* this image's rows and columns, 1..8192 */
+  int32_t a_lo, a_hi;  /* RandomResizedCrop's area range for THIS image: max(1, ceil(scale0*Hs*Ws)),
+                          max(a_lo, floor(scale1*Hs*Ws)) -- the formulas lbt_batch_resized_crop documents */
+  int32_t ch, cw;      /* this image's validation box, 1 <= ch <= Hs, 1 <= cw <= Ws */
+} lbt_image_geom;
+/* lbt_batch_resized_crop on a ragged store: (Hs, Ws, a_lo, a_hi, ch, cw) are replaced by geom, a device array
+ * of [n_data] records, and data_bytes, the size of data. Sample b takes source s = idx ? idx[b] : first + b,
+ * reads geom[s], and every formula of lbt_batch_resized_crop then applies with that record's Hs, Ws, a_lo,
+ * a_hi, ch, cw on the image at data + offset: the box, its ten attempts and three fallback branches, the flip,
+ * the taps, the blend and the normalisation. The draw's key stays base + b, not s: two shards with their
+ * bases equal one batch. q_lo, q_hi, ratio_q16, shift and scale_c are global, as there. A store of equal
+ * images with the table spelling out the uniform arguments equals lbt_batch_resized_crop bit for bit.
+ * A source outside [0, n_data) reads neither the table nor the store: a zero image and label -1. The records
+ * (device memory) are the caller's to keep valid, as idx's values are: lbt_image_geom_check states what valid
+ * means and checks a host copy; the launch cannot. As a last defence a record whose image does not lie
+ * inside [0, data_bytes), or whose fields are out of the ranges above, is not read through either (a zero
+ * image, label -1); that is no contract to build on. Stream-ordered, no allocation, capturable. LBT_EINVAL
+ * before any HIP call: what lbt_batch_resized_crop refuses of the arguments that remain (a NULL data / labels
+ * / X / y / ratio_q16 / shift / scale_c; B / C / Ho / Wo / n_data <= 0; Ho or Wo > 8192; Ho*Wo*C >= 2^31;
+ * q_lo < 1, q_hi < q_lo, q_hi >= 2^32; base < 0 or base + B > 2^32; idx == NULL with first < 0 or first + B >
+ * n_data), a NULL geom, data_bytes <= 0. 16-byte stores when (Wo*C) % 4 == 0 and X is 16-byte aligned, else
+ * 4-byte: the same values. (Added under ABI 24.)                                                        */
+int lbt_batch_ragged_crop(const uint8_t* data, int64_t data_bytes, const lbt_image_geom* geom,
+                          const int32_t* labels, int64_t n_data, const int32_t* idx, int64_t first, float* X,
+                          int32_t* y, int32_t B, int32_t C, int32_t Ho, int32_t Wo, int32_t augment,
+                          const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, const double* shift,
+                          const double* scale_c, int64_t base, uint64_t seed, uint64_t counter, void* stream);
+/* lbt_batch_resized_crop_jitter on a ragged store, by the same replacement: the same two launches, the same
+ * "CJT!" draw keyed base + b, the same integer definitions, and the same scratch,
+ * lbt_batch_resized_crop_jitter_work(B, Ho) entries (the strips depend on B and Ho only). augment == 0 is
+ * lbt_batch_ragged_crop. LBT_EINVAL before any HIP call: everything lbt_batch_ragged_crop refuses, and C,
+ * the six bounds, work and work_len as lbt_batch_resized_crop_jitter refuses them. (Added under ABI 24.)   */
+int lbt_batch_ragged_crop_jitter(const uint8_t* data, int64_t data_bytes, const lbt_image_geom* geom,
+                                 const int32_t* labels, int64_t n_data, const int32_t* idx, int64_t first, float* X,
+                                 int32_t* y, int32_t B, int32_t C, int32_t Ho, int32_t Wo, int32_t augment,
+                                 const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, const double* shift,
+                                 const double* scale_c, int64_t base, uint64_t seed, uint64_t counter, int32_t fb_lo,
+                                 int32_t fb_hi, int32_t fc_lo, int32_t fc_hi, int32_t fs_lo, int32_t fs_hi,
+                                 uint64_t* work, int64_t work_len, void* stream);
+/* Whether a HOST copy of a table is valid for a store of data_bytes bytes of C-channel images (host only, no
+ * HIP call): -1 when every record is, else the index of the first that is not -- offset < 0, offset + Hs*Ws*C
+ * > data_bytes, Hs or Ws outside [1, 8192], Hs*Ws*C >= 2^31, a_lo < 1, a_hi < a_lo, a_hi > Hs*Ws, ch outside
+ * [1, Hs] or cw outside [1, Ws]. -2 for a NULL table or n_data / C / data_bytes <= 0. Records may overlap or
+ * repeat (an image stored once may be listed twice), and no alignment is asked of offset: the kernels load
+ * bytes. (Added under ABI 24.)                                                                          */
+int64_t lbt_image_geom_check(const lbt_image_geom* host_geom, int64_t n_data, int32_t C, int64_t data_bytes);
+
 /* Diagnostics: counts (atomically into *bad) the i < n where the BN kernels' division by a
  * reused divisor (div_by(x, recip(y)), dfxp_device.h) differs in any bit from x / y; if qa
  * is not NULL also writes x / y to qa and div_by to qb.                                      */
@@ -1224,7 +1276,9 @@ int lbt_dfxp_range_pick(const uint64_t* tables, const int32_t* slots, int32_t nj
  * of lbt_conv_fwd_fused_i8 / lbt_conv_fwd2_fused_i8 keeps it: no entry point or struct layout changed, a
  * frozen chain used to return LBT_EINVAL. lbt_dropout_*_at, lbt_bias_grad_x, lbt_batch_gather,
  * lbt_batch_resized_crop, lbt_batch_resized_crop_jitter (+ _work), lbt_summary_*, lbt_augment_flip_crop_at, lbt_eval_tally and lbt_dfxp_range_scan / _pick are additions under the same number: every
- * earlier signature and result stands.                                                              */
+ * earlier signature and result stands. So are lbt_image_geom, lbt_batch_ragged_crop, lbt_batch_ragged_crop_jitter
+ * and lbt_image_geom_check (the ragged image store): lbt_batch_resized_crop and its _jitter keep their
+ * signatures and compute what they computed.                                                        */
 int lbt_abi_version(void);
 
 #ifdef __cplusplus

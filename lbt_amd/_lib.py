@@ -198,6 +198,16 @@ class Summary(ctypes.Structure):
                 ("ring", c_void_p), ("capacity", c_int64), ("cursor", c_void_p), ("scratch", c_void_p)]
 
 
+class ImageGeom(ctypes.Structure):
+    """lbt_image_geom: one image of a ragged store (32 bytes, no padding)."""
+    _fields_ = [("offset", c_int64), ("Hs", c_int32), ("Ws", c_int32), ("a_lo", c_int32), ("a_hi", c_int32),
+                ("ch", c_int32), ("cw", c_int32)]
+
+
+# the same record as a numpy structured dtype: a table is one array of these, on the host and on the device
+IMAGE_GEOM_DTYPE = [("offset", "<i8"), ("Hs", "<i4"), ("Ws", "<i4"), ("a_lo", "<i4"), ("a_hi", "<i4"), ("ch", "<i4"),
+                    ("cw", "<i4")]
+
 SUMMARY_CHUNK = 16384  # LBT_SUMMARY_CHUNK
 RANGE_BINS = 61  # LBT_RANGE_BINS: a calibration table's entries, I = -30 .. 30
 
@@ -349,6 +359,12 @@ _SIGS = {
                                       _P, c_int64, c_uint64, c_uint64, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, _P, c_int64, _P],
     "lbt_batch_resized_crop_jitter_work": [c_int32, c_int32],
+    "lbt_batch_ragged_crop": [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32,
+                              c_int32, _P, c_int64, c_int64, _P, _P, c_int64, c_uint64, c_uint64, _P],
+    "lbt_batch_ragged_crop_jitter": [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32,
+                                     c_int32, c_int32, _P, c_int64, c_int64, _P, _P, c_int64, c_uint64, c_uint64,
+                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P],
+    "lbt_image_geom_check": [_P, c_int64, c_int32, c_int64],
     "lbt_step_update": [_P, _P, _P, c_int64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_int32, _P, _P],
     "lbt_summary_record_bytes": [c_int32, c_int32],
     "lbt_summary_scratch_bytes": [c_int32, c_int64],
@@ -379,7 +395,7 @@ def load(path=LIB_PATH):
         fn.argtypes = argtypes
         fn.restype = c_int32
     for name in ("lbt_igemm_workspace_bytes", "lbt_summary_record_bytes", "lbt_summary_scratch_bytes",
-                 "lbt_batch_resized_crop_jitter_work"):
+                 "lbt_batch_resized_crop_jitter_work", "lbt_image_geom_check"):
         getattr(lib, name).restype = c_int64  # the int64-valued queries
     if lib.lbt_abi_version() != ABI_VERSION:
         raise ImportError("lbt_amd ABI mismatch: library %d, bindings %d" % (lib.lbt_abi_version(), ABI_VERSION))

@@ -9,6 +9,8 @@
 //                      subtract-multiply per element (below, at its kernel)
 //   lbt_batch_resized_crop_jitter   the same with ColorJitter's brightness, contrast and saturation between the
 //                      resample and the normalisation, in integers (at the end of this file)
+//   lbt_batch_ragged_crop (+ _jitter)   the same two on a store of images of differing size: the same kernels,
+//                      instantiated to read each sample's geometry from a table (rrc_geom)
 //
 // lbt_batch_gather: one workgroup per output sample: the source index and the Philox draw depend on blockIdx only, so
 // they are wave-uniform. A streaming pass bound by its stores (4 B written per byte read): each lane
@@ -157,7 +159,48 @@ struct RrcArgs {
   uint64_t seed, counter;
 };
 
+// A ragged store's launch: [n_data] records in place of Hs, Ws, a_lo, a_span, ch, cw (which it leaves unread).
+// Appended, so that the uniform kernels keep the argument block, and with it the code, they had.
+struct RaggedArgs : RrcArgs {
+  const lbt_image_geom* geom;
+  int64_t data_bytes;
+};
+
+template <bool RAGGED>
+using RrcArgsT = std::conditional_t<RAGGED, RaggedArgs, RrcArgs>;
+
 struct Box { uint32_t top, left, h, w; };
+
+// What a ragged store has per image and a uniform one per launch. A function of the source sample, which is a
+// function of blockIdx.x and the arguments: wave-uniform, like everything derived from it (the box, the row
+// stride, the 64-bit image base). A RAGGED kernel reads it from the table with scalar loads -- the address
+// holds no lane index and nothing the kernel stores precedes the load -- and the uniform instantiation
+// copies its arguments (and forms the image base where it always did: img stays unused).
+struct Geom {
+  uint32_t Hs, Ws, a_lo, a_span, ch, cw;
+  const uint8_t* img;  // RAGGED: the image's first pixel
+  bool ok;             // there is an image to read
+};
+
+template <bool RAGGED>
+LBT_DEV Geom rrc_geom(const RrcArgsT<RAGGED>& a, int64_t s) {
+  const bool ok = s >= 0 && s < a.n_data;
+  if constexpr (!RAGGED) {
+    return Geom{a.Hs, a.Ws, a.a_lo, a.a_span, a.ch, a.cw, nullptr, ok};
+  } else {
+    const Geom none{1, 1, 1, 1, 1, 1, a.data, false};  // a box of one pixel that is never read
+    if (!ok) return none;
+    const lbt_image_geom r = a.geom[s];
+    // The host cannot see the table (lbt_dfxp.h): a record lbt_image_geom_check would refuse is not read through.
+    const int64_t px = (int64_t)r.Hs * r.Ws;
+    if (r.Hs < 1 || r.Hs > 8192 || r.Ws < 1 || r.Ws > 8192 || r.offset < 0 || px * a.C >= ((int64_t)1 << 31) ||
+        r.offset > a.data_bytes - px * a.C || r.a_lo < 1 || r.a_hi < r.a_lo || r.a_hi > px || r.ch < 1 || r.ch > r.Hs ||
+        r.cw < 1 || r.cw > r.Ws)
+      return none;
+    return Geom{(uint32_t)r.Hs, (uint32_t)r.Ws, (uint32_t)r.a_lo, (uint32_t)(r.a_hi - r.a_lo + 1), (uint32_t)r.ch,
+                (uint32_t)r.cw, a.data + r.offset, true};
+  }
+}
 
 // floor(sqrt(x)), x < 2^62: the float64 root is within one of it, the loops settle the rest exactly
 LBT_DEV uint64_t isqrt64(uint64_t x) {
@@ -168,13 +211,13 @@ LBT_DEV uint64_t isqrt64(uint64_t x) {
 }
 
 // The crop box of sample n: RandomResizedCrop.get_params in integers, or the central (ch, cw) box.
-LBT_DEV Box rrc_box(const RrcArgs& a, uint32_t n) {
-  const uint64_t Hs = a.Hs, Ws = a.Ws;
-  if (!a.augment) return Box{(a.Hs - a.ch) / 2, (a.Ws - a.cw) / 2, a.ch, a.cw};
+LBT_DEV Box rrc_box(const RrcArgs& a, const Geom& g, uint32_t n) {
+  const uint64_t Hs = g.Hs, Ws = g.Ws;
+  if (!a.augment) return Box{(g.Hs - g.ch) / 2, (g.Ws - g.cw) / 2, g.ch, g.cw};
   for (uint32_t t = 0; t < 10; ++t) {
     const U4 r = philox(n, kRrcStream + t, (uint32_t)a.counter, (uint32_t)(a.counter >> 32), (uint32_t)a.seed,
                         (uint32_t)(a.seed >> 32));
-    const uint64_t area = (uint64_t)a.a_lo + r.x % a.a_span;  // <= Hs*Ws <= 2^26
+    const uint64_t area = (uint64_t)g.a_lo + r.x % g.a_span;  // <= Hs*Ws <= 2^26
     const uint64_t q = a.ratio[r.y >> 24];
     if (q == 0) continue;  // (no table the host builds holds one: q >= q_lo >= 1)
     const uint64_t w = (isqrt64((4 * area * q) >> 16) + 1) >> 1;  // rint(sqrt(area * ratio)); 4aq < 2^60
@@ -205,24 +248,26 @@ LBT_DEV uint32_t rrc_tap(uint32_t i, uint32_t in, uint32_t out) {
   return p0 | f << 13 | (p0 + 1 <= in - 1 ? 1u : 0u) << 22;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(kT) void resized_crop_kernel(const RrcArgs a) {
+template <bool VEC, bool RAGGED>
+__global__ __launch_bounds__(kT) void resized_crop_kernel(const RrcArgsT<RAGGED> a) {
   extern __shared__ uint32_t tab[];  // [Wo] column taps, [rows] this strip's row taps
   const uint32_t b = blockIdx.x, i0 = blockIdx.y * a.rows;
   const uint32_t nrow = a.Ho - i0 < a.rows ? a.Ho - i0 : a.rows;
   const int64_t s = a.idx ? (int64_t)a.idx[b] : a.first + (int64_t)b;
-  const bool ok = s >= 0 && s < a.n_data;
+  const Geom gm = rrc_geom<RAGGED>(a, s);
+  const bool ok = gm.ok;
   const uint32_t key = (uint32_t)(a.base + (int64_t)b);
-  const Box box = rrc_box(a, key);
+  const Box box = rrc_box(a, gm, key);
   const bool fl = a.augment && (philox(key, kAugStream, (uint32_t)a.counter, (uint32_t)(a.counter >> 32),
                                        (uint32_t)a.seed, (uint32_t)(a.seed >> 32)).x & 1u);
   for (uint32_t j = threadIdx.x; j < a.Wo; j += kT) tab[j] = rrc_tap(fl ? a.Wo - 1 - j : j, box.w, a.Wo);
   for (uint32_t i = threadIdx.x; i < nrow; i += kT) tab[a.Wo + i] = rrc_tap(i0 + i, box.h, a.Ho);
   if (blockIdx.y == 0 && threadIdx.x == 0) a.y[b] = ok ? a.labels[s] : -1;
   __syncthreads();
-  const uint32_t WoC = a.Wo * a.C, rs = a.Ws * a.C, total = nrow * WoC;  // < 2^31 (host checks)
-  const uint8_t* __restrict__ src =
-      a.data + (ok ? s * (int64_t)a.Hs * rs : 0) + ((int64_t)box.top * a.Ws + box.left) * a.C;
+  const uint32_t WoC = a.Wo * a.C, rs = gm.Ws * a.C, total = nrow * WoC;  // < 2^31 (host checks)
+  const uint8_t* img = gm.img;
+  if constexpr (!RAGGED) img = a.data + (ok ? s * (int64_t)a.Hs * rs : 0);  // (formed here, as it always was)
+  const uint8_t* __restrict__ src = img + ((int64_t)box.top * gm.Ws + box.left) * a.C;
   float* __restrict__ out = a.X + ((int64_t)b * a.Ho + i0) * (int64_t)WoC;
   constexpr uint32_t kV = VEC ? 4u : 1u;
   if (!ok) {  // (uniform) nothing to read: a zero image
@@ -289,6 +334,64 @@ __global__ __launch_bounds__(kT) void resized_crop_kernel(const RrcArgs a) {
   }
 }
 
+// rows of a strip: about 1024 workgroups (four per CU) however small the batch; 2048 measured slower: every
+// strip redoes the box. A function of B and Ho alone, which the jitter's scratch size follows.
+int32_t rrc_strip_rows(int32_t B, int32_t Ho) {
+  const int32_t want = (1024 + B - 1) / B;
+  const int32_t rows = (Ho + want - 1) / want;
+  return rows < 1 ? 1 : rows > kRrcMaxRows ? kRrcMaxRows : rows;
+}
+
+// What the entry points share, checked and packed: everything but the store's geometry. false: LBT_EINVAL.
+bool rrc_pack(RrcArgs& a, const uint8_t* data, const int32_t* labels, int64_t n_data, const int32_t* idx, int64_t first,
+              float* X, int32_t* y, int32_t B, int32_t C, int32_t Ho, int32_t Wo, int32_t augment,
+              const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, const double* shift, const double* scale_c,
+              int64_t base, uint64_t seed, uint64_t counter) {
+  if (!data || !labels || !X || !y || !ratio_q16 || !shift || !scale_c) return false;
+  if (B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || n_data <= 0) return false;
+  if (Ho > 8192 || Wo > 8192 || (int64_t)Ho * Wo * C >= ((int64_t)1 << 31)) return false;
+  if (q_lo < 1 || q_hi < q_lo || q_hi > 0xFFFFFFFFLL) return false;
+  if (base < 0 || base > ((int64_t)1 << 32) - B) return false;  // the draw's key is 32 bits wide
+  if (!idx && (first < 0 || first > n_data - B)) return false;
+  a.data = data; a.labels = labels; a.n_data = n_data; a.idx = idx; a.first = first; a.X = X; a.y = y;
+  a.C = (uint32_t)C; a.Ho = (uint32_t)Ho; a.Wo = (uint32_t)Wo;
+  a.rows = (uint32_t)rrc_strip_rows(B, Ho); a.augment = augment != 0;
+  a.ratio = ratio_q16; a.q_lo = (uint32_t)q_lo; a.q_hi = (uint32_t)q_hi;
+  a.shift = shift; a.scale = scale_c; a.base = base; a.seed = seed; a.counter = counter;
+  a.Hs = a.Ws = a.a_lo = a.a_span = a.ch = a.cw = 0;
+  return true;
+}
+
+// One stored size for every image (C as rrc_pack checked it)
+bool rrc_pack_uniform(RrcArgs& a, int32_t Hs, int32_t Ws, int64_t a_lo, int64_t a_hi, int32_t ch, int32_t cw) {
+  if (Hs <= 0 || Ws <= 0 || Hs > 8192 || Ws > 8192 || (int64_t)Hs * Ws * a.C >= ((int64_t)1 << 31)) return false;
+  if (a_lo < 1 || a_hi < a_lo || a_hi > (int64_t)Hs * Ws) return false;
+  if (ch < 1 || ch > Hs || cw < 1 || cw > Ws) return false;
+  a.Hs = (uint32_t)Hs; a.Ws = (uint32_t)Ws; a.a_lo = (uint32_t)a_lo; a.a_span = (uint32_t)(a_hi - a_lo + 1);
+  a.ch = (uint32_t)ch; a.cw = (uint32_t)cw;
+  return true;
+}
+
+// A table of sizes: its records are on the device, so only the pointer and the size can be refused here
+bool rrc_pack_ragged(RaggedArgs& a, const lbt_image_geom* geom, int64_t data_bytes) {
+  if (!geom || data_bytes <= 0) return false;
+  a.geom = geom; a.data_bytes = data_bytes;
+  return true;
+}
+
+dim3 rrc_grid(const RrcArgs& a, int32_t B) { return dim3((unsigned)B, (unsigned)((a.Ho + a.rows - 1) / a.rows)); }
+size_t rrc_lds(const RrcArgs& a) { return sizeof(uint32_t) * (size_t)(a.Wo + a.rows); }
+
+template <bool RAGGED>
+int rrc_launch(const RrcArgsT<RAGGED>& a, int32_t B, void* stream) {
+  const bool vec = ((int64_t)a.Wo * a.C) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL((resized_crop_kernel<true, RAGGED>), rrc_grid(a, B), dim3(kT), rrc_lds(a), (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((resized_crop_kernel<false, RAGGED>), rrc_grid(a, B), dim3(kT), rrc_lds(a), (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" int lbt_batch_resized_crop(const uint8_t* data, const int32_t* labels, int64_t n_data, const int32_t* idx,
@@ -297,35 +400,39 @@ extern "C" int lbt_batch_resized_crop(const uint8_t* data, const int32_t* labels
                                       const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, int32_t ch, int32_t cw,
                                       const double* shift, const double* scale_c, int64_t base, uint64_t seed,
                                       uint64_t counter, void* stream) {
-  if (!data || !labels || !X || !y || !ratio_q16 || !shift || !scale_c) return LBT_EINVAL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || n_data <= 0) return LBT_EINVAL;
-  if (Hs > 8192 || Ws > 8192 || Ho > 8192 || Wo > 8192) return LBT_EINVAL;
-  if ((int64_t)Hs * Ws * C >= ((int64_t)1 << 31) || (int64_t)Ho * Wo * C >= ((int64_t)1 << 31)) return LBT_EINVAL;
-  if (a_lo < 1 || a_hi < a_lo || a_hi > (int64_t)Hs * Ws) return LBT_EINVAL;
-  if (q_lo < 1 || q_hi < q_lo || q_hi > 0xFFFFFFFFLL) return LBT_EINVAL;
-  if (ch < 1 || ch > Hs || cw < 1 || cw > Ws) return LBT_EINVAL;
-  if (base < 0 || base > ((int64_t)1 << 32) - B) return LBT_EINVAL;  // the draw's key is 32 bits wide
-  if (!idx && (first < 0 || first > n_data - B)) return LBT_EINVAL;
-  // strips: about 1024 workgroups (four per CU) however small the batch; 2048 measured slower: every strip redoes the box
-  const int32_t want = (1024 + B - 1) / B;
-  int32_t rows = (Ho + want - 1) / want;
-  rows = rows < 1 ? 1 : rows > kRrcMaxRows ? kRrcMaxRows : rows;
-  const int32_t strips = (Ho + rows - 1) / rows;
   RrcArgs a;
-  a.data = data; a.labels = labels; a.n_data = n_data; a.idx = idx; a.first = first; a.X = X; a.y = y;
-  a.Hs = (uint32_t)Hs; a.Ws = (uint32_t)Ws; a.C = (uint32_t)C; a.Ho = (uint32_t)Ho; a.Wo = (uint32_t)Wo;
-  a.rows = (uint32_t)rows; a.augment = augment != 0;
-  a.a_lo = (uint32_t)a_lo; a.a_span = (uint32_t)(a_hi - a_lo + 1);
-  a.ratio = ratio_q16; a.q_lo = (uint32_t)q_lo; a.q_hi = (uint32_t)q_hi; a.ch = (uint32_t)ch; a.cw = (uint32_t)cw;
-  a.shift = shift; a.scale = scale_c; a.base = base; a.seed = seed; a.counter = counter;
-  const bool vec = ((int64_t)Wo * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  const dim3 grid((unsigned)B, (unsigned)strips);
-  const size_t lds = sizeof(uint32_t) * (size_t)(Wo + rows);
-  if (vec)
-    hipLaunchKernelGGL((resized_crop_kernel<true>), grid, dim3(kT), lds, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((resized_crop_kernel<false>), grid, dim3(kT), lds, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  if (!rrc_pack(a, data, labels, n_data, idx, first, X, y, B, C, Ho, Wo, augment, ratio_q16, q_lo, q_hi, shift, scale_c,
+                base, seed, counter) ||
+      !rrc_pack_uniform(a, Hs, Ws, a_lo, a_hi, ch, cw))
+    return LBT_EINVAL;
+  return rrc_launch<false>(a, B, stream);
+}
+
+extern "C" int lbt_batch_ragged_crop(const uint8_t* data, int64_t data_bytes, const lbt_image_geom* geom,
+                                     const int32_t* labels, int64_t n_data, const int32_t* idx, int64_t first, float* X,
+                                     int32_t* y, int32_t B, int32_t C, int32_t Ho, int32_t Wo, int32_t augment,
+                                     const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi, const double* shift,
+                                     const double* scale_c, int64_t base, uint64_t seed, uint64_t counter,
+                                     void* stream) {
+  RaggedArgs a;
+  if (!rrc_pack(a, data, labels, n_data, idx, first, X, y, B, C, Ho, Wo, augment, ratio_q16, q_lo, q_hi, shift, scale_c,
+                base, seed, counter) ||
+      !rrc_pack_ragged(a, geom, data_bytes))
+    return LBT_EINVAL;
+  return rrc_launch<true>(a, B, stream);
+}
+
+extern "C" int64_t lbt_image_geom_check(const lbt_image_geom* host_geom, int64_t n_data, int32_t C, int64_t data_bytes) {
+  if (!host_geom || n_data <= 0 || C <= 0 || data_bytes <= 0) return -2;
+  for (int64_t i = 0; i < n_data; ++i) {
+    const lbt_image_geom& r = host_geom[i];
+    if (r.Hs < 1 || r.Hs > 8192 || r.Ws < 1 || r.Ws > 8192) return i;
+    const int64_t px = (int64_t)r.Hs * r.Ws, bytes = px * C;  // <= 2^26 * C: no overflow
+    if (bytes >= ((int64_t)1 << 31) || r.offset < 0 || r.offset > data_bytes - bytes) return i;
+    if (r.a_lo < 1 || r.a_hi < r.a_lo || r.a_hi > px) return i;
+    if (r.ch < 1 || r.ch > r.Hs || r.cw < 1 || r.cw > r.Ws) return i;
+  }
+  return -1;
 }
 
 // ------------------------------------------------------------------ lbt_batch_resized_crop_jitter
@@ -346,8 +453,9 @@ constexpr int32_t kJitOne = 4096;       // Q12 factor 1: every operation returns
 constexpr uint32_t kJitStream = 0x434A5421u;  // "CJT!"
 enum : uint32_t { kOpB = 0, kOpC = 1, kOpS = 2 };
 
-struct JitArgs {
-  RrcArgs r;
+template <bool RAGGED>
+struct JitArgsT {
+  RrcArgsT<RAGGED> r;
   uint32_t fb_lo, fb_span, fc_lo, fc_span, fs_lo, fs_span;  // factor = lo + draw % span
   uint64_t* work;  // [B][strips] sums of grey, or NULL with contrast off
   uint32_t strips;
@@ -363,6 +471,7 @@ struct Jit {
 
 LBT_DEV int32_t jit_factor(const Jit& j, uint32_t op) { return (int32_t)((j.f >> (17 * op)) & 0x1FFFFu); }
 
+template <class JitArgs>
 LBT_DEV Jit jit_draw(const JitArgs& a, uint32_t key) {
   const U4 r = philox(key, kJitStream, (uint32_t)a.r.counter, (uint32_t)(a.r.counter >> 32), (uint32_t)a.r.seed,
                       (uint32_t)(a.r.seed >> 32));
@@ -430,19 +539,22 @@ struct JitStrip {
   uint32_t i0, nrow;
   bool ok;
   const uint8_t* src;
+  uint32_t rs;  // the source image's row stride in bytes
   Jit j;
 };
 
-LBT_DEV JitStrip jit_prologue(const JitArgs& ja, uint32_t* tab, bool write_label) {
-  const RrcArgs& a = ja.r;
+template <bool RAGGED>
+LBT_DEV JitStrip jit_prologue(const JitArgsT<RAGGED>& ja, uint32_t* tab, bool write_label) {
+  const RrcArgsT<RAGGED>& a = ja.r;
   JitStrip s;
   const uint32_t b = blockIdx.x;
   s.i0 = blockIdx.y * a.rows;
   s.nrow = a.Ho - s.i0 < a.rows ? a.Ho - s.i0 : a.rows;
   const int64_t sm = a.idx ? (int64_t)a.idx[b] : a.first + (int64_t)b;
-  s.ok = sm >= 0 && sm < a.n_data;
+  const Geom gm = rrc_geom<RAGGED>(a, sm);
+  s.ok = gm.ok;
   const uint32_t key = (uint32_t)(a.base + (int64_t)b);
-  const Box box = rrc_box(a, key);
+  const Box box = rrc_box(a, gm, key);
   const bool fl = a.augment && (philox(key, kAugStream, (uint32_t)a.counter, (uint32_t)(a.counter >> 32),
                                        (uint32_t)a.seed, (uint32_t)(a.seed >> 32)).x & 1u);
   s.j = jit_draw(ja, key);
@@ -450,19 +562,22 @@ LBT_DEV JitStrip jit_prologue(const JitArgs& ja, uint32_t* tab, bool write_label
   for (uint32_t i = threadIdx.x; i < s.nrow; i += kT) tab[a.Wo + i] = rrc_tap(s.i0 + i, box.h, a.Ho);
   if (write_label && blockIdx.y == 0 && threadIdx.x == 0) a.y[b] = s.ok ? a.labels[sm] : -1;
   __syncthreads();
-  s.src = a.data + (s.ok ? sm * (int64_t)a.Hs * a.Ws * 3 : 0) + ((int64_t)box.top * a.Ws + box.left) * 3;
+  const uint8_t* img = gm.img;
+  if constexpr (!RAGGED) img = a.data + (s.ok ? sm * (int64_t)a.Hs * a.Ws * 3 : 0);  // (formed here, as it always was)
+  s.src = img + ((int64_t)box.top * gm.Ws + box.left) * 3;
+  s.rs = gm.Ws * 3;
   return s;
 }
 
 // The strip's sum of grey over the pixels as they stand before contrast -> work[sample][strip]. kP as in
 // jitter_out_kernel: the same threads take the same pixels.
-template <uint32_t kP>
-__global__ __launch_bounds__(kT) void jitter_stats_kernel(const JitArgs ja) {
+template <uint32_t kP, bool RAGGED>
+__global__ __launch_bounds__(kT) void jitter_stats_kernel(const JitArgsT<RAGGED> ja) {
   extern __shared__ uint32_t tab[];  // [Wo] column taps, [rows] this strip's row taps
   __shared__ long long red[kT / 64];
   const RrcArgs& a = ja.r;
-  const JitStrip s = jit_prologue(ja, tab, false);
-  const uint32_t rs = a.Ws * 3;
+  const JitStrip s = jit_prologue<RAGGED>(ja, tab, false);
+  const uint32_t rs = s.rs;
   const uint32_t Q = a.Wo / kP, Qc = Q < (uint32_t)kT ? Q : (uint32_t)kT, G = (uint32_t)kT / Qc;
   const uint32_t g = threadIdx.x / Qc, q0 = threadIdx.x - g * Qc;
   uint64_t sum = 0;  // <= rows * Wo * kJitT < 2^50
@@ -504,12 +619,12 @@ __global__ __launch_bounds__(kT) void jitter_stats_kernel(const JitArgs ja) {
 // resized_crop_kernel with the jitter between the blend and the normalisation. kP pixels per thread: 4 (Wo % 4
 // == 0: the twelve floats stay inside the row, 16-byte aligned with X; written as three float4, which the
 // compiler is free to regroup), or 1.
-template <uint32_t kP>
-__global__ __launch_bounds__(kT) void jitter_out_kernel(const JitArgs ja) {
+template <uint32_t kP, bool RAGGED>
+__global__ __launch_bounds__(kT) void jitter_out_kernel(const JitArgsT<RAGGED> ja) {
   extern __shared__ uint32_t tab[];
   const RrcArgs& a = ja.r;
-  const JitStrip s = jit_prologue(ja, tab, true);
-  const uint32_t WoC = a.Wo * 3, rs = a.Ws * 3, total = s.nrow * WoC;  // < 2^31 (host checks)
+  const JitStrip s = jit_prologue<RAGGED>(ja, tab, true);
+  const uint32_t WoC = a.Wo * 3, rs = s.rs, total = s.nrow * WoC;  // < 2^31 (host checks)
   float* __restrict__ out = a.X + ((int64_t)blockIdx.x * a.Ho + s.i0) * (int64_t)WoC;
   if (!s.ok) {  // (uniform) nothing to read: a zero image
     constexpr uint32_t kV = kP == 4 ? 4u : 1u;
@@ -576,20 +691,60 @@ __global__ __launch_bounds__(kT) void jitter_out_kernel(const JitArgs ja) {
   }
 }
 
-// rows of a strip: lbt_batch_resized_crop's policy (about 1024 workgroups), which the scratch size follows
-int32_t jitter_strip_rows(int32_t B, int32_t Ho) {
-  const int32_t want = (1024 + B - 1) / B;
-  const int32_t rows = (Ho + want - 1) / want;
-  return rows < 1 ? 1 : rows > kRrcMaxRows ? kRrcMaxRows : rows;
+bool jitter_range_ok(int32_t lo, int32_t hi) { return 0 <= lo && lo <= hi && hi <= 65536; }
+
+// What the jitter adds to its plain launch's arguments. stats: whether the statistics pass runs.
+struct JitHost {
+  int32_t fb_lo, fb_hi, fc_lo, fc_hi, fs_lo, fs_hi;
+  uint64_t* work;
+  int64_t work_len;
+  bool stats;
+};
+
+// The jitter's own refusals, made before its plain launch's. false: LBT_EINVAL.
+bool jitter_own_ok(JitHost& j, int32_t B, int32_t C, int32_t Ho, int32_t augment) {
+  if (C != 3) return false;
+  if (!jitter_range_ok(j.fb_lo, j.fb_hi) || !jitter_range_ok(j.fc_lo, j.fc_hi) || !jitter_range_ok(j.fs_lo, j.fs_hi))
+    return false;
+  j.stats = augment != 0 && !(j.fc_lo == kJitOne && j.fc_hi == kJitOne);
+  return !(j.stats && (B <= 0 || Ho <= 0 || Ho > 8192 || !j.work ||
+                       j.work_len < lbt_batch_resized_crop_jitter_work(B, Ho)));
 }
 
-bool jitter_range_ok(int32_t lo, int32_t hi) { return 0 <= lo && lo <= hi && hi <= 65536; }
+// The statistics pass (with contrast on) and the output pass, on the plain launch's packed arguments.
+template <bool RAGGED>
+int jitter_launch(const RrcArgsT<RAGGED>& r, const JitHost& j, int32_t B, void* stream) {
+  JitArgsT<RAGGED> ja;
+  ja.r = r;
+  ja.fb_lo = (uint32_t)j.fb_lo; ja.fb_span = (uint32_t)(j.fb_hi - j.fb_lo + 1);
+  ja.fc_lo = (uint32_t)j.fc_lo; ja.fc_span = (uint32_t)(j.fc_hi - j.fc_lo + 1);
+  ja.fs_lo = (uint32_t)j.fs_lo; ja.fs_span = (uint32_t)(j.fs_hi - j.fs_lo + 1);
+  ja.work = j.stats ? j.work : nullptr;
+  const dim3 grid = rrc_grid(r, B);
+  ja.strips = grid.y;
+  const bool vec = r.Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(r.X) & 15) == 0;
+  const size_t lds = rrc_lds(r);
+  hipStream_t st = (hipStream_t)stream;
+  if (j.stats) {
+    if (vec)
+      hipLaunchKernelGGL((jitter_stats_kernel<4, RAGGED>), grid, dim3(kT), lds, st, ja);
+    else
+      hipLaunchKernelGGL((jitter_stats_kernel<1, RAGGED>), grid, dim3(kT), lds, st, ja);
+    const int e = (int)hipGetLastError();
+    if (e) return e;
+  }
+  if (vec)
+    hipLaunchKernelGGL((jitter_out_kernel<4, RAGGED>), grid, dim3(kT), lds, st, ja);
+  else
+    hipLaunchKernelGGL((jitter_out_kernel<1, RAGGED>), grid, dim3(kT), lds, st, ja);
+  return (int)hipGetLastError();
+}
 
 }  // namespace
 
 extern "C" int64_t lbt_batch_resized_crop_jitter_work(int32_t B, int32_t Ho) {
   if (B <= 0 || Ho <= 0 || Ho > 8192) return -1;
-  const int32_t rows = jitter_strip_rows(B, Ho);
+  const int32_t rows = rrc_strip_rows(B, Ho);
   return (int64_t)B * ((Ho + rows - 1) / rows);
 }
 
@@ -601,54 +756,31 @@ extern "C" int lbt_batch_resized_crop_jitter(const uint8_t* data, const int32_t*
                                              const double* scale_c, int64_t base, uint64_t seed, uint64_t counter,
                                              int32_t fb_lo, int32_t fb_hi, int32_t fc_lo, int32_t fc_hi, int32_t fs_lo,
                                              int32_t fs_hi, uint64_t* work, int64_t work_len, void* stream) {
-  if (C != 3) return LBT_EINVAL;
-  if (!jitter_range_ok(fb_lo, fb_hi) || !jitter_range_ok(fc_lo, fc_hi) || !jitter_range_ok(fs_lo, fs_hi))
+  JitHost j{fb_lo, fb_hi, fc_lo, fc_hi, fs_lo, fs_hi, work, work_len, false};
+  RrcArgs a;
+  if (!jitter_own_ok(j, B, C, Ho, augment) ||
+      !rrc_pack(a, data, labels, n_data, idx, first, X, y, B, C, Ho, Wo, augment, ratio_q16, q_lo, q_hi, shift, scale_c,
+                base, seed, counter) ||
+      !rrc_pack_uniform(a, Hs, Ws, a_lo, a_hi, ch, cw))
     return LBT_EINVAL;
-  const bool stats = augment != 0 && !(fc_lo == kJitOne && fc_hi == kJitOne);
-  if (stats && (B <= 0 || Ho <= 0 || Ho > 8192 || !work || work_len < lbt_batch_resized_crop_jitter_work(B, Ho)))
+  // the validation transform: no jitter, the plain launch
+  return augment ? jitter_launch<false>(a, j, B, stream) : rrc_launch<false>(a, B, stream);
+}
+
+extern "C" int lbt_batch_ragged_crop_jitter(const uint8_t* data, int64_t data_bytes, const lbt_image_geom* geom,
+                                            const int32_t* labels, int64_t n_data, const int32_t* idx, int64_t first,
+                                            float* X, int32_t* y, int32_t B, int32_t C, int32_t Ho, int32_t Wo,
+                                            int32_t augment, const uint32_t* ratio_q16, int64_t q_lo, int64_t q_hi,
+                                            const double* shift, const double* scale_c, int64_t base, uint64_t seed,
+                                            uint64_t counter, int32_t fb_lo, int32_t fb_hi, int32_t fc_lo, int32_t fc_hi,
+                                            int32_t fs_lo, int32_t fs_hi, uint64_t* work, int64_t work_len,
+                                            void* stream) {
+  JitHost j{fb_lo, fb_hi, fc_lo, fc_hi, fs_lo, fs_hi, work, work_len, false};
+  RaggedArgs a;
+  if (!jitter_own_ok(j, B, C, Ho, augment) ||
+      !rrc_pack(a, data, labels, n_data, idx, first, X, y, B, C, Ho, Wo, augment, ratio_q16, q_lo, q_hi, shift, scale_c,
+                base, seed, counter) ||
+      !rrc_pack_ragged(a, geom, data_bytes))
     return LBT_EINVAL;
-  if (!augment)  // the validation transform: no jitter, the plain launch (which makes every other check)
-    return lbt_batch_resized_crop(data, labels, n_data, idx, first, X, y, B, Hs, Ws, C, Ho, Wo, augment, a_lo, a_hi,
-                                  ratio_q16, q_lo, q_hi, ch, cw, shift, scale_c, base, seed, counter, stream);
-  if (!data || !labels || !X || !y || !ratio_q16 || !shift || !scale_c) return LBT_EINVAL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 || n_data <= 0) return LBT_EINVAL;
-  if (Hs > 8192 || Ws > 8192 || Ho > 8192 || Wo > 8192) return LBT_EINVAL;
-  if ((int64_t)Hs * Ws * C >= ((int64_t)1 << 31) || (int64_t)Ho * Wo * C >= ((int64_t)1 << 31)) return LBT_EINVAL;
-  if (a_lo < 1 || a_hi < a_lo || a_hi > (int64_t)Hs * Ws) return LBT_EINVAL;
-  if (q_lo < 1 || q_hi < q_lo || q_hi > 0xFFFFFFFFLL) return LBT_EINVAL;
-  if (ch < 1 || ch > Hs || cw < 1 || cw > Ws) return LBT_EINVAL;
-  if (base < 0 || base > ((int64_t)1 << 32) - B) return LBT_EINVAL;  // the draw's key is 32 bits wide
-  if (!idx && (first < 0 || first > n_data - B)) return LBT_EINVAL;
-  const int32_t rows = jitter_strip_rows(B, Ho);
-  const int32_t strips = (Ho + rows - 1) / rows;
-  JitArgs ja;
-  RrcArgs& a = ja.r;
-  a.data = data; a.labels = labels; a.n_data = n_data; a.idx = idx; a.first = first; a.X = X; a.y = y;
-  a.Hs = (uint32_t)Hs; a.Ws = (uint32_t)Ws; a.C = 3; a.Ho = (uint32_t)Ho; a.Wo = (uint32_t)Wo;
-  a.rows = (uint32_t)rows; a.augment = 1;
-  a.a_lo = (uint32_t)a_lo; a.a_span = (uint32_t)(a_hi - a_lo + 1);
-  a.ratio = ratio_q16; a.q_lo = (uint32_t)q_lo; a.q_hi = (uint32_t)q_hi; a.ch = (uint32_t)ch; a.cw = (uint32_t)cw;
-  a.shift = shift; a.scale = scale_c; a.base = base; a.seed = seed; a.counter = counter;
-  ja.fb_lo = (uint32_t)fb_lo; ja.fb_span = (uint32_t)(fb_hi - fb_lo + 1);
-  ja.fc_lo = (uint32_t)fc_lo; ja.fc_span = (uint32_t)(fc_hi - fc_lo + 1);
-  ja.fs_lo = (uint32_t)fs_lo; ja.fs_span = (uint32_t)(fs_hi - fs_lo + 1);
-  ja.work = stats ? work : nullptr;
-  ja.strips = (uint32_t)strips;
-  const bool vec = Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  const dim3 grid((unsigned)B, (unsigned)strips);
-  const size_t lds = sizeof(uint32_t) * (size_t)(Wo + rows);
-  hipStream_t st = (hipStream_t)stream;
-  if (stats) {
-    if (vec)
-      hipLaunchKernelGGL((jitter_stats_kernel<4>), grid, dim3(kT), lds, st, ja);
-    else
-      hipLaunchKernelGGL((jitter_stats_kernel<1>), grid, dim3(kT), lds, st, ja);
-    const int e = (int)hipGetLastError();
-    if (e) return e;
-  }
-  if (vec)
-    hipLaunchKernelGGL((jitter_out_kernel<4>), grid, dim3(kT), lds, st, ja);
-  else
-    hipLaunchKernelGGL((jitter_out_kernel<1>), grid, dim3(kT), lds, st, ja);
-  return (int)hipGetLastError();
+  return augment ? jitter_launch<true>(a, j, B, stream) : rrc_launch<true>(a, B, stream);
 }

@@ -12,11 +12,15 @@ A ``ResizedCropDataset`` is the same for the reference's ImageNet pipeline (``da
 of one stored size on the device, and one ``lbt_batch_resized_crop`` launch per batch for
 ``RandomResizedCrop`` + ``RandomHorizontalFlip`` (or the validation centre crop), the bilinear resample and
 ``Normalize``; with ``color_jitter`` the training launch (``lbt_batch_resized_crop_jitter``) also applies
-``ColorJitter``'s brightness, contrast and saturation. Both classes give the Trainer's loops ``sample_shape``, ``train_batch`` and ``test_batch``.
+``ColorJitter``'s brightness, contrast and saturation. A ``RaggedCropDataset`` is that pipeline on images
+of their own sizes, as the reference runs it: one byte array and a table of per-image geometry on the
+device, and the same kernels reading each sample's record (``lbt_batch_ragged_crop`` / ``_jitter``). All
+three classes give the Trainer's loops ``sample_shape``, ``train_batch`` and ``test_batch``.
 """
 import numpy as np
 import torch
 
+from . import _lib
 from .dfxp import ops
 
 
@@ -147,45 +151,32 @@ def _jitter_range(v, name):
     return int(np.rint(4096 * lo)), int(np.rint(4096 * hi))
 
 
-class ResizedCropDataset:
-    """The reference's ImageNet pipeline (``data.py:58-93``) from device memory: X [n, Hs, Ws, C] uint8 of
-    one stored size (resized offline, e.g. to 256 x 256), y [n] integer labels; ``mean`` / ``std`` per
-    channel in ``Normalize``'s units (of pixel / 255); ``size`` the output (Ho, Wo), or one int for both.
+def _area_range(s0, s1, Hs, Ws):
+    """RandomResizedCrop's area range (a_lo, a_hi), in pixels, inside a stored Hs x Ws -- ints, or int arrays
+    for a table of images: the same float64 products either way."""
+    a_lo = np.maximum(1, np.ceil(s0 * Hs * Ws).astype(np.int64))
+    a_hi = np.maximum(a_lo, np.floor(s1 * Hs * Ws).astype(np.int64))
+    return a_lo, a_hi
 
-    ``batch(augment=True)`` is the training transform -- ``RandomResizedCrop(size, scale, ratio)``,
-    ``RandomHorizontalFlip``, ``ToTensor``, ``Normalize`` -- and ``batch()`` the validation one: the central
-    ``center`` = (ch, cw) box (default 7/8 of the store: 224 of 256, ``Resize(256)`` + ``CenterCrop(224)`` on a
-    256 x 256 store) resampled to ``size``. One ``lbt_batch_resized_crop`` launch writes the fp32 batch; the
-    transform is defined in integers (include/lbt_dfxp.h) on the constants prepared here once: ``a_lo``,
-    ``a_hi`` (the box's area in pixels), ``ratio_q16`` (256 log-uniform aspect ratios, Q16), ``q_lo``,
-    ``q_hi``, ``shift`` and ``scale_c`` (float64 per channel). Bilinear without antialiasing: keep the store
-    near the output size.
 
-    ``color_jitter`` = (brightness, contrast, saturation), each a scalar or a (min, max) pair with
-    torchvision's meaning, adds ``ColorJitter`` to the training transform (three-channel stores; hue is not
-    built: a fourth entry must be zero): ``batch(augment=True)`` then launches
-    ``lbt_batch_resized_crop_jitter``, which draws each sample's order and factors from the Q12 ranges
-    ``fb_lo`` .. ``fs_hi`` (``jitter`` holds all six) and works in integers on the resampled pixel. ``batch()``
-    and ``test_batch`` never jitter. None: the launch is ``lbt_batch_resized_crop``."""
+class _CropDataset:
+    """What ResizedCropDataset and RaggedCropDataset share: everything about the transform that does not depend
+    on an image's stored size -- the labels, the output size, ``Normalize``'s constants, the aspect-ratio
+    table, the colour jitter and its scratch -- and the batch interface the Trainer's loops call. A subclass
+    holds the store (``_data``) with its geometry and makes the launch (``_launch``)."""
 
-    def __init__(self, X, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None,
-                 color_jitter=None):
-        X, y = _host(X), _host(y)
-        if X.dtype != np.uint8:
-            raise TypeError("ResizedCropDataset holds uint8 images, got %s" % X.dtype)
-        if X.ndim != 4:
-            raise ValueError("X must be [n, Hs, Ws, C], got shape %s" % (X.shape,))
+    def _init_pipeline(self, y, n, C, mean, std, size, scale, ratio, color_jitter, device):
+        y = _host(y)
         if not np.issubdtype(y.dtype, np.integer):
             raise TypeError("labels must be integers, got %s" % y.dtype)
-        if y.ndim != 1 or len(y) != len(X):
-            raise ValueError("X holds %d samples, y %s" % (len(X), y.shape))
-        if len(X) == 0:
+        if y.ndim != 1 or len(y) != n:
+            raise ValueError("the store holds %d samples, y %s" % (n, y.shape))
+        if n == 0:
             raise ValueError("an empty dataset")
-        n, Hs, Ws, C = X.shape
         Ho, Wo = (size, size) if isinstance(size, (int, np.integer)) else tuple(size)
         Ho, Wo = int(Ho), int(Wo)
-        if min(Hs, Ws, C, Ho, Wo) < 1 or max(Hs, Ws, Ho, Wo) > 8192:
-            raise ValueError("stored and output sizes must lie in [1, 8192], got %dx%d -> %dx%d" % (Hs, Ws, Ho, Wo))
+        if min(C, Ho, Wo) < 1 or max(Ho, Wo) > 8192:
+            raise ValueError("the output size must lie in [1, 8192] with a channel or more, got %dx%dx%d" % (Ho, Wo, C))
         mean, std = (np.array(_host(v), dtype=np.float64).reshape(-1) for v in (mean, std))
         if mean.shape != (C,) or std.shape != (C,):
             raise ValueError("mean and std must hold one value per channel (%d)" % C)
@@ -197,8 +188,7 @@ class ResizedCropDataset:
             raise ValueError("scale must satisfy 0 < scale[0] <= scale[1] <= 1, got %s" % (scale,))
         if not 0 < r0 <= r1:
             raise ValueError("ratio must satisfy 0 < ratio[0] <= ratio[1], got %s" % (ratio,))
-        self.a_lo = max(1, int(np.ceil(s0 * Hs * Ws)))
-        self.a_hi = max(self.a_lo, int(np.floor(s1 * Hs * Ws)))
+        self.scale_range = (s0, s1)
         k = (np.arange(256, dtype=np.float64) + 0.5) / 256
         self.ratio_q16 = np.rint(65536 * np.exp(np.log(r0) + k * (np.log(r1) - np.log(r0))))
         self.q_lo, self.q_hi = int(np.rint(65536 * r0)), int(np.rint(65536 * r1))
@@ -207,11 +197,6 @@ class ResizedCropDataset:
         self.ratio_q16 = self.ratio_q16.astype(np.uint32)
         self.shift = 65536.0 * 255.0 * mean
         self.scale_c = 1.0 / (65536.0 * 255.0 * std)
-        if center is None:
-            center = ((7 * Hs + 4) // 8, (7 * Ws + 4) // 8)
-        self.center = (int(center[0]), int(center[1]))
-        if not (1 <= self.center[0] <= Hs and 1 <= self.center[1] <= Ws):
-            raise ValueError("the centre box %s does not fit the stored %dx%d" % (self.center, Hs, Ws))
         self.jitter = None
         if color_jitter is not None:
             cj = tuple(color_jitter)
@@ -225,18 +210,17 @@ class ResizedCropDataset:
                 _jitter_range(v, name) for v, name in zip(cj, ("brightness", "contrast", "saturation")))
             self.jitter = (self.fb_lo, self.fb_hi, self.fc_lo, self.fc_hi, self.fs_lo, self.fs_hi)
         self._work = {}  # batch size -> the contrast pass's scratch, allocated at first use and kept
-        self.shape = tuple(X.shape)
+        self._n = n
         self.sample_shape = (Ho, Wo, C)
         self.mean, self.std = mean, std
         self.device = torch.device(device if device is not None else "cuda")
-        self._data = torch.from_numpy(np.ascontiguousarray(X)).to(self.device)
         self._labels = torch.from_numpy(y.astype(np.int32)).to(self.device)
         self._ratio = torch.from_numpy(self.ratio_q16.view(np.int32).copy()).to(self.device)  # the bit patterns
         self._shift = torch.from_numpy(self.shift).to(self.device)
         self._scale = torch.from_numpy(self.scale_c).to(self.device)
 
     def __len__(self):
-        return self.shape[0]
+        return self._n
 
     upload_index = DeviceDataset.upload_index
 
@@ -259,15 +243,9 @@ class ResizedCropDataset:
             lo, hi = torch.aminmax(idx)
             if int(lo) < 0 or int(hi) >= len(self):
                 raise IndexError("idx out of range for a dataset of %d samples" % len(self))
-        if augment and self.jitter is not None:
-            ops.batch_resized_crop_jitter(self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale,
-                                          a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi,
-                                          center=self.center, jitter=self.jitter, work=self._jitter_work(B), idx=idx,
-                                          first=first, augment=True, base=base, seed=seed, counter=counter)
-            return out_X, out_y
-        ops.batch_resized_crop(self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale,
-                               a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi, center=self.center,
-                               idx=idx, first=first, augment=augment, base=base, seed=seed, counter=counter)
+        work = {"jitter": self.jitter, "work": self._jitter_work(B)} if augment and self.jitter is not None else None
+        self._launch(out_X, out_y, work, idx=idx, first=first, augment=bool(augment), base=base, seed=seed,
+                     counter=counter)
         return out_X, out_y
 
     def _jitter_work(self, B):
@@ -291,4 +269,148 @@ class ResizedCropDataset:
         return self.batch(out_X, out_y, first=first)
 
 
-DEVICE_DATASETS = (DeviceDataset, ResizedCropDataset)  # what Trainer.train() / evaluate() take in place of arrays
+class ResizedCropDataset(_CropDataset):
+    """The reference's ImageNet pipeline (``data.py:58-93``) from device memory: X [n, Hs, Ws, C] uint8 of
+    one stored size (resized offline, e.g. to 256 x 256), y [n] integer labels; ``mean`` / ``std`` per
+    channel in ``Normalize``'s units (of pixel / 255); ``size`` the output (Ho, Wo), or one int for both.
+
+    ``batch(augment=True)`` is the training transform -- ``RandomResizedCrop(size, scale, ratio)``,
+    ``RandomHorizontalFlip``, ``ToTensor``, ``Normalize`` -- and ``batch()`` the validation one: the central
+    ``center`` = (ch, cw) box (default 7/8 of the store: 224 of 256, ``Resize(256)`` + ``CenterCrop(224)`` on a
+    256 x 256 store) resampled to ``size``. One ``lbt_batch_resized_crop`` launch writes the fp32 batch; the
+    transform is defined in integers (include/lbt_dfxp.h) on the constants prepared here once: ``a_lo``,
+    ``a_hi`` (the box's area in pixels), ``ratio_q16`` (256 log-uniform aspect ratios, Q16), ``q_lo``,
+    ``q_hi``, ``shift`` and ``scale_c`` (float64 per channel). Bilinear without antialiasing: keep the store
+    near the output size. Images of their own sizes: ``RaggedCropDataset``.
+
+    ``color_jitter`` = (brightness, contrast, saturation), each a scalar or a (min, max) pair with
+    torchvision's meaning, adds ``ColorJitter`` to the training transform (three-channel stores; hue is not
+    built: a fourth entry must be zero): ``batch(augment=True)`` then launches
+    ``lbt_batch_resized_crop_jitter``, which draws each sample's order and factors from the Q12 ranges
+    ``fb_lo`` .. ``fs_hi`` (``jitter`` holds all six) and works in integers on the resampled pixel. ``batch()``
+    and ``test_batch`` never jitter. None: the launch is ``lbt_batch_resized_crop``."""
+
+    def __init__(self, X, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None,
+                 color_jitter=None):
+        X = _host(X)
+        if X.dtype != np.uint8:
+            raise TypeError("ResizedCropDataset holds uint8 images, got %s" % X.dtype)
+        if X.ndim != 4:
+            raise ValueError("X must be [n, Hs, Ws, C], got shape %s" % (X.shape,))
+        n, Hs, Ws, C = X.shape
+        if n and (min(Hs, Ws) < 1 or max(Hs, Ws) > 8192):
+            raise ValueError("the stored size must lie in [1, 8192], got %dx%d" % (Hs, Ws))
+        self._init_pipeline(y, n, C, mean, std, size, scale, ratio, color_jitter, device)
+        self.a_lo, self.a_hi = (int(v) for v in _area_range(*self.scale_range, Hs, Ws))
+        if center is None:
+            center = ((7 * Hs + 4) // 8, (7 * Ws + 4) // 8)
+        self.center = (int(center[0]), int(center[1]))
+        if not (1 <= self.center[0] <= Hs and 1 <= self.center[1] <= Ws):
+            raise ValueError("the centre box %s does not fit the stored %dx%d" % (self.center, Hs, Ws))
+        self.shape = tuple(X.shape)
+        self._data = torch.from_numpy(np.ascontiguousarray(X)).to(self.device)
+
+    def _launch(self, out_X, out_y, jitter, **kw):
+        args = (self._data, self._labels, out_X, out_y, self._ratio, self._shift, self._scale)
+        geo = dict(a_lo=self.a_lo, a_hi=self.a_hi, q_lo=self.q_lo, q_hi=self.q_hi, center=self.center)
+        if jitter is not None:
+            ops.batch_resized_crop_jitter(*args, **geo, **jitter, **kw)
+        else:
+            ops.batch_resized_crop(*args, **geo, **kw)
+
+
+class RaggedCropDataset(_CropDataset):
+    """ResizedCropDataset for images of differing stored size -- the reference's pipeline as it runs on real
+    data (``data.py:58-93``): ``RandomResizedCrop`` draws its box inside each image's own H x W, and validation
+    is ``Resize(256)`` of the short side, aspect ratio kept, + ``CenterCrop(224)``. ``images`` is a sequence of
+    uint8 arrays [H_i, W_i, C] with one C (resized offline, e.g. to a short side of 256); every other argument
+    keeps its meaning.
+
+    The store is one byte array on the device, the images packed densely in order, beside a table of one
+    ``lbt_image_geom`` record per image (``geom``, a numpy array of ``_lib.IMAGE_GEOM_DTYPE``): the image's
+    byte offset, its H and W, its own area range ``a_lo`` / ``a_hi`` -- ResizedCropDataset's expressions on its
+    own H x W -- and its validation box. ``center=None`` makes that box the square of side ``(7 * min(H, W) + 4)
+    // 8``: 224 of a short side of 256, where the resample to ``size`` = 224 is the identity and a validation
+    batch holds the image's central 224 x 224 pixels, normalised: the reference's validation transform exactly.
+    ``center=(ch, cw)`` asks for those pixels of every image. The launches are ``lbt_batch_ragged_crop`` and,
+    with ``color_jitter``, ``lbt_batch_ragged_crop_jitter``; the table is checked here
+    (``lbt_image_geom_check``), once, because the launch cannot.
+
+    The whole store lies in device memory: sized for sets that fit it (a short-side-256 ImageNet-1k does not fit
+    one GPU's HBM)."""
+
+    def __init__(self, images, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None, device=None,
+                 color_jitter=None):
+        images = [_host(im) for im in images]
+        if not images:
+            raise ValueError("an empty dataset")
+        for i, im in enumerate(images):
+            if im.dtype != np.uint8:
+                raise TypeError("RaggedCropDataset holds uint8 images, image %d is %s" % (i, im.dtype))
+            if im.ndim != 3:
+                raise ValueError("image %d must be [H, W, C], got shape %s" % (i, im.shape))
+            if im.shape[2] != images[0].shape[2]:
+                raise ValueError("image %d has %d channels, image 0 has %d" % (i, im.shape[2], images[0].shape[2]))
+        shapes = np.array([im.shape[:2] for im in images], dtype=np.int64)
+        data = np.concatenate([im.reshape(-1) for im in images])
+        self._build(data, shapes, images[0].shape[2], y, mean, std, size, scale, ratio, center, device, color_jitter)
+
+    @classmethod
+    def from_flat(cls, data, shapes, y, mean, std, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), center=None,
+                  device=None, color_jitter=None):
+        """The same from a store already packed: ``data`` a one-dimensional uint8 array holding the images
+        densely in order, ``shapes`` [n, 2] their (H, W). The channel count is ``mean``'s length. The host
+        array is uploaded as it is, never copied."""
+        data, shapes = _host(data), _host(shapes)
+        if data.dtype != np.uint8:
+            raise TypeError("RaggedCropDataset holds uint8 images, got %s" % data.dtype)
+        if data.ndim != 1:
+            raise ValueError("data must be one-dimensional, got shape %s" % (data.shape,))
+        if not np.issubdtype(shapes.dtype, np.integer) or shapes.ndim != 2 or shapes.shape[1] != 2:
+            raise ValueError("shapes must be [n, 2] integers, got %s %s" % (shapes.dtype, shapes.shape))
+        self = cls.__new__(cls)
+        self._build(data, shapes.astype(np.int64), int(np.size(_host(mean))), y, mean, std, size, scale, ratio, center,
+                    device, color_jitter)
+        return self
+
+    def _build(self, data, shapes, C, y, mean, std, size, scale, ratio, center, device, color_jitter):
+        n = len(shapes)
+        H, W = shapes[:, 0], shapes[:, 1]
+        bad = np.flatnonzero((H < 1) | (H > 8192) | (W < 1) | (W > 8192))
+        if bad.size:
+            raise ValueError("image %d: the stored size must lie in [1, 8192], got %dx%d" % (bad[0], H[bad[0]], W[bad[0]]))
+        nbytes = H * W * C
+        if int(nbytes.sum()) != data.size:
+            raise ValueError("the images hold %d bytes at %d channels, data %d" % (nbytes.sum(), C, data.size))
+        self._init_pipeline(y, n, C, mean, std, size, scale, ratio, color_jitter, device)
+        if center is None:
+            ch = cw = (7 * np.minimum(H, W) + 4) // 8
+        else:
+            center = (int(center[0]), int(center[1]))
+            ch, cw = np.full(n, center[0], dtype=np.int64), np.full(n, center[1], dtype=np.int64)
+        self.center = center
+        bad = np.flatnonzero((ch < 1) | (ch > H) | (cw < 1) | (cw > W))
+        if bad.size:
+            i = bad[0]
+            raise ValueError("image %d: the centre box (%d, %d) does not fit the stored %dx%d" % (i, ch[i], cw[i], H[i], W[i]))
+        geom = np.zeros(n, dtype=np.dtype(_lib.IMAGE_GEOM_DTYPE))
+        geom["offset"] = np.cumsum(nbytes) - nbytes
+        geom["Hs"], geom["Ws"], geom["ch"], geom["cw"] = H, W, ch, cw
+        geom["a_lo"], geom["a_hi"] = _area_range(*self.scale_range, H, W)
+        i = ops.image_geom_check(geom, C, data.size)
+        if i != -1:
+            raise ValueError("image %d: its record %s is not valid for a store of %d bytes" % (i, geom[max(i, 0)], data.size))
+        self.geom, self.shapes, self.channels = geom, shapes, C
+        self._data = torch.from_numpy(np.ascontiguousarray(data)).to(self.device)
+        self._geom = torch.from_numpy(geom.view(np.uint8).reshape(n, geom.itemsize)).to(self.device)
+
+    def _launch(self, out_X, out_y, jitter, **kw):
+        args = (self._data, self._geom, self._labels, out_X, out_y, self._ratio, self._shift, self._scale)
+        if jitter is not None:
+            ops.batch_ragged_crop_jitter(*args, q_lo=self.q_lo, q_hi=self.q_hi, **jitter, **kw)
+        else:
+            ops.batch_ragged_crop(*args, q_lo=self.q_lo, q_hi=self.q_hi, **kw)
+
+
+# what Trainer.train() / evaluate() take in place of arrays
+DEVICE_DATASETS = (DeviceDataset, ResizedCropDataset, RaggedCropDataset)

@@ -4,6 +4,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -838,6 +839,22 @@ def batch_resized_crop_jitter_work(B, Ho):
     return n
 
 
+def _jitter_arguments(name, C, B, Ho, jitter, work, augment):
+    """The jitter's own checks, for either store: (the six bounds as ints, work's length)."""
+    if C != 3:
+        raise ValueError("%s: colour jitter needs three channels, data has %d" % (name, C))
+    jitter = tuple(int(v) for v in jitter)
+    if len(jitter) != 6 or any(not 0 <= lo <= hi <= 65536 for lo, hi in zip(jitter[::2], jitter[1::2])):
+        raise ValueError("%s: six Q12 bounds with 0 <= lo <= hi <= 65536, got %s" % (name, jitter))
+    work_len = 0
+    if work is not None:
+        _check(work, torch.int64, "work")
+        work_len = work.numel()
+    if augment and jitter[2:4] != (4096, 4096) and work_len < batch_resized_crop_jitter_work(B, Ho):
+        raise ValueError("%s: work must hold %d entries, got %d" % (name, batch_resized_crop_jitter_work(B, Ho), work_len))
+    return jitter, work_len
+
+
 def batch_resized_crop_jitter(data, labels, out_X, out_y, ratio_q16, shift, scale_c, *, a_lo, a_hi, q_lo, q_hi, center,
                               jitter, work=None, idx=None, first=0, augment=False, base=0, seed=0, counter=0):
     """batch_resized_crop with ColorJitter's brightness, contrast and saturation between the resample and the
@@ -847,23 +864,81 @@ def batch_resized_crop_jitter(data, labels, out_X, out_y, ratio_q16, shift, scal
     None only with contrast off (fc_lo == fc_hi == 4096). augment=False ignores the jitter."""
     n, Hs, Ws, C, B, Ho, Wo = _resized_crop_shapes("batch_resized_crop_jitter", data, labels, out_X, out_y, ratio_q16,
                                                    shift, scale_c, idx)
-    if C != 3:
-        raise ValueError("batch_resized_crop_jitter: colour jitter needs three channels, data has %d" % C)
-    jitter = tuple(int(v) for v in jitter)
-    if len(jitter) != 6 or any(not 0 <= lo <= hi <= 65536 for lo, hi in zip(jitter[::2], jitter[1::2])):
-        raise ValueError("batch_resized_crop_jitter: six Q12 bounds with 0 <= lo <= hi <= 65536, got %s" % (jitter,))
-    work_len = 0
-    if work is not None:
-        _check(work, torch.int64, "work")
-        work_len = work.numel()
-    if augment and jitter[2:4] != (4096, 4096) and work_len < batch_resized_crop_jitter_work(B, Ho):
-        raise ValueError("batch_resized_crop_jitter: work must hold %d entries, got %d"
-                         % (batch_resized_crop_jitter_work(B, Ho), work_len))
+    jitter, work_len = _jitter_arguments("batch_resized_crop_jitter", C, B, Ho, jitter, work, augment)
     call("lbt_batch_resized_crop_jitter", ptr(data), ptr(labels), n, ptr(idx), int(first), ptr(out_X), ptr(out_y), B,
          Hs, Ws, C, Ho, Wo, int(bool(augment)), int(a_lo), int(a_hi), ptr(ratio_q16), int(q_lo), int(q_hi),
          int(center[0]), int(center[1]), ptr(shift), ptr(scale_c), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF,
          int(counter) & 0xFFFFFFFFFFFFFFFF, *jitter, ptr(work), work_len, stream())
     return out_X, out_y
+
+
+def _ragged_crop_shapes(name, data, geom, labels, out_X, out_y, ratio_q16, shift, scale_c, idx):
+    """The dtype / device / shape checks of batch_ragged_crop and batch_ragged_crop_jitter: (data_bytes, n, C, B,
+    Ho, Wo)."""
+    _check(data, torch.uint8, "data")
+    _check(geom, torch.uint8, "geom")
+    _check(labels, torch.int32, "labels")
+    _check(out_X, torch.float32, "out_X")
+    _check(out_y, torch.int32, "out_y")
+    _check(ratio_q16, torch.int32, "ratio_q16")
+    _check(shift, torch.float64, "shift")
+    _check(scale_c, torch.float64, "scale_c")
+    if data.dim() != 1 or data.numel() == 0:
+        raise ValueError("%s: data must be the store's bytes, one dimension, got shape %s" % (name, tuple(data.shape)))
+    n = labels.numel()
+    if geom.dim() != 2 or tuple(geom.shape) != (n, ctypes.sizeof(_lib.ImageGeom)):
+        raise ValueError("%s: geom must hold one %d-byte record per label (%d), got shape %s"
+                         % (name, ctypes.sizeof(_lib.ImageGeom), n, tuple(geom.shape)))
+    if out_X.dim() != 4 or out_y.numel() != out_X.shape[0]:
+        raise ValueError("%s: out_X must be [B, Ho, Wo, C] and out_y [B], got %s and %s"
+                         % (name, tuple(out_X.shape), tuple(out_y.shape)))
+    B, Ho, Wo, C = out_X.shape
+    if ratio_q16.numel() != 256 or shift.numel() != C or scale_c.numel() != C:
+        raise ValueError("%s: ratio_q16 must hold 256 entries, shift and scale_c one per channel" % name)
+    if idx is not None:
+        _check(idx, torch.int32, "idx")
+        if idx.numel() != B:
+            raise ValueError("idx must hold one source index per output sample")
+    return data.numel(), n, C, B, Ho, Wo
+
+
+def batch_ragged_crop(data, geom, labels, out_X, out_y, ratio_q16, shift, scale_c, *, q_lo, q_hi, idx=None, first=0,
+                      augment=False, base=0, seed=0, counter=0):
+    """batch_resized_crop on a store of images of differing size (lbt_batch_ragged_crop): data is the store's
+    bytes, one dimension, and geom [n, 32] uint8 the bytes of n lbt_image_geom records (offset, Hs, Ws, a_lo,
+    a_hi, ch, cw: _lib.IMAGE_GEOM_DTYPE), which take the place of the stored size, the area range and the
+    centre box. Sample b reads the record of its source sample; its draw stays that of sample base + b. The
+    records are the caller's to keep valid (lbt_amd.data.RaggedCropDataset builds and checks them)."""
+    nbytes, n, C, B, Ho, Wo = _ragged_crop_shapes("batch_ragged_crop", data, geom, labels, out_X, out_y, ratio_q16,
+                                                  shift, scale_c, idx)
+    call("lbt_batch_ragged_crop", ptr(data), nbytes, ptr(geom), ptr(labels), n, ptr(idx), int(first), ptr(out_X),
+         ptr(out_y), B, C, Ho, Wo, int(bool(augment)), ptr(ratio_q16), int(q_lo), int(q_hi), ptr(shift), ptr(scale_c),
+         int(base), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, stream())
+    return out_X, out_y
+
+
+def batch_ragged_crop_jitter(data, geom, labels, out_X, out_y, ratio_q16, shift, scale_c, *, q_lo, q_hi, jitter,
+                             work=None, idx=None, first=0, augment=False, base=0, seed=0, counter=0):
+    """batch_ragged_crop with ColorJitter's brightness, contrast and saturation (lbt_batch_ragged_crop_jitter;
+    three channels). jitter and work as in batch_resized_crop_jitter, the scratch size included:
+    batch_resized_crop_jitter_work(B, Ho). augment=False ignores the jitter."""
+    nbytes, n, C, B, Ho, Wo = _ragged_crop_shapes("batch_ragged_crop_jitter", data, geom, labels, out_X, out_y,
+                                                  ratio_q16, shift, scale_c, idx)
+    jitter, work_len = _jitter_arguments("batch_ragged_crop_jitter", C, B, Ho, jitter, work, augment)
+    call("lbt_batch_ragged_crop_jitter", ptr(data), nbytes, ptr(geom), ptr(labels), n, ptr(idx), int(first),
+         ptr(out_X), ptr(out_y), B, C, Ho, Wo, int(bool(augment)), ptr(ratio_q16), int(q_lo), int(q_hi), ptr(shift),
+         ptr(scale_c), int(base), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, *jitter, ptr(work),
+         work_len, stream())
+    return out_X, out_y
+
+
+def image_geom_check(geom, C, data_bytes):
+    """lbt_image_geom_check on a host table (a numpy array of _lib.IMAGE_GEOM_DTYPE records): -1 when every
+    record is valid for a store of data_bytes bytes of C-channel images, else the first bad record's index (-2:
+    no table, or a non-positive C / data_bytes)."""
+    geom = np.ascontiguousarray(geom, dtype=np.dtype(_lib.IMAGE_GEOM_DTYPE))
+    return int(_lib.load().lbt_image_geom_check(geom.ctypes.data_as(ctypes.c_void_p) if geom.size else None,
+                                                int(geom.size), int(C), int(data_bytes)))
 
 
 def maxpool_fwd(x, y, amax, d):

@@ -726,7 +726,8 @@ class Trainer:
         Returns the per-epoch test accuracies.
         A dataset (DeviceDataset, DeviceDataset | None) (lbt_amd.data) runs the same epochs from device
         memory: see _train_device. A pair of ResizedCropDataset runs them with the ImageNet transforms
-        (the random box and flip per training sample when augmenting, the centre crop for the test loop).
+        (the random box and flip per training sample when augmenting, the centre crop for the test loop); a
+        pair of RaggedCropDataset the same from images of their own sizes.
         Under a process group of ``world`` > 1 ranks (a data-parallel trainer) the epoch is sharded:
         ``batch_size`` stays the GLOBAL batch (trainer.py:34); rank 0 draws the epoch's permutation where
         the single process draws it and broadcasts it (one small collective per epoch, outside any
@@ -792,7 +793,7 @@ class Trainer:
         every 100 batches). The gather is launched ahead of the step's graph, not captured into it: its
         arguments change every step. Bit for bit the host loop on ds.host_float(). (A ResizedCropDataset:
         the same loop with one lbt_batch_resized_crop (or, with color_jitter, _jitter) launch per step, through the classes' common
-        train_batch / test_batch / sample_shape.)
+        train_batch / test_batch / sample_shape; a RaggedCropDataset: lbt_batch_ragged_crop / _jitter, likewise.)
         Sharded (see train()): every rank holds the whole dataset on its GPU and uploads the broadcast
         permutation; rank r's launch gathers idx = perm[b + r*s : b + (r+1)*s] with base = r*s into a
         buffer pair of the shard's size s = nb / world."""
